@@ -22,6 +22,15 @@ alternate over three library contexts, each with its own stream, workspace
 and outputs, so one pair's memory-bound index build overlaps the previous
 pairs' latency-bound queries. Every step still processes one whole pair.
 
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the --steps timed steps, the result line. `--full` adds the measurements that
+take runs of their own after the timed steps (CPU baselines, isolated kernel
+durations, STREAM-copy ceiling, K4 without the gather, K5's copy floor and
+trace comparison); a plain line carries null in their places.
+`--dump-outputs DIR` writes the last timed step's outputs as DIR/<name>.npy
+(dump_outputs); the inputs are seeded, so two runs with the same arguments
+see the same data.
+
 Launch: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either
 under torch.distributed.run (--nproc-per-node N, one rank per GPU, RCCL), or
 plain `python bench.py --gpus N`, which starts that launcher itself as a child
@@ -102,6 +111,15 @@ def parse():
     p.add_argument("--no-stream-copy", action="store_true",
                    help="skip the STREAM-copy ceiling measurement")
     p.add_argument("--json-out", default=None)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure, each in runs of its "
+                        "own after the timed steps: the CPU baselines, the isolated kernel "
+                        "durations (--iso-steps), the STREAM-copy ceiling, k4 on N > 1 ranks "
+                        "without the gather, k5's copy floor and its pose chain against the "
+                        "oracle trace. Without it the line carries null in their places")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as "
+                        "DIR/<name>.npy (float32 or float64, see dump_outputs)")
     p.add_argument("--dry-run", action="store_true",
                    help="rank plumbing only (no GPU): every rank joins a gloo group, takes "
                         "its K4 shard of --pairs and reports; rank 0 prints one JSON line")
@@ -208,6 +226,43 @@ def median_after_warmup(fn, reps):
         fn()
         ts.append(time.perf_counter() - t0)
     return float(np.median(ts)), ts
+
+
+DUMP_BUDGET = 60_000_000  # bytes over all the files of one --dump-outputs
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: write `arrays` (name -> numpy array) as
+    <dirname>/<name>.npy. Floating-point arrays are written as float64;
+    integer arrays (masks, indices) as float32 when every value is exact in
+    it (|v| <= 2^24), else as float64. The files together stay within `budget`
+    bytes: taken from the smallest up, an array larger than its even share
+    of what is left is written as a sample of its rows (all but the last
+    axis flattened), the rows drawn once without replacement by numpy's
+    PCG64 seeded with 0 and kept in ascending order, so the same arguments
+    select the same rows in every run and every build."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        if v.dtype.kind in "iub" and (v.size == 0 or (int(v.min()) >= -(1 << 24)
+                                                      and int(v.max()) <= 1 << 24)):
+            conv[name] = v.astype(np.float32)
+        else:
+            conv[name] = v.astype(np.float64)
+    left = budget
+    order = sorted(conv, key=lambda n: conv[n].nbytes)
+    for i, name in enumerate(order):
+        v = conv[name]
+        share = left // (len(order) - i)
+        if v.nbytes > share and v.ndim >= 1:
+            rows = v.reshape(-1, v.shape[-1]) if v.ndim > 1 else v.reshape(-1, 1)
+            keep = max(1, share // max(rows[0].nbytes, 1))
+            pick = np.sort(np.random.Generator(np.random.PCG64(0)).choice(
+                rows.shape[0], size=keep, replace=False))
+            v = rows[pick] if v.ndim > 1 else rows[pick, 0]
+        left -= v.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
 
 
 def _ref_lib():
@@ -420,11 +475,19 @@ def run_k5(a, ws, rank, dev):
     frames_all = shard.sum_over_ranks(a.steps, dev)
     if rank != 0:
         return None
-    floor = k5_copy_floor(L, ctx, pcs, attr, R * Cc)
-    cpu = None
-    if not a.no_cpu_baseline and a.cpu_frames > 0:
-        cpu = cpu_baseline_k5(frames, F, min(a.cpu_frames, len(poses)), poses)
-    vs_trace = k5_vs_trace(poses, frames, R, Cc, F, 11 + rank, a.warmup)
+    if a.dump_outputs and a.steps > 0:
+        # the last timed frame's pose (what slam_localization returned), and
+        # the chain of the timed frames that led to it
+        dump_outputs(a.dump_outputs, {"pose": np.asarray(poses[-1], np.float64),
+                                      "pose_chain": np.asarray(poses[-a.steps:], np.float64)})
+    # --full only: the copy floor, the CPU run and the trace comparison are
+    # runs and checks of their own beside the headline figure
+    floor = cpu = vs_trace = None
+    if a.full:
+        floor = k5_copy_floor(L, ctx, pcs, attr, R * Cc)
+        if not a.no_cpu_baseline and a.cpu_frames > 0:
+            cpu = cpu_baseline_k5(frames, F, min(a.cpu_frames, len(poses)), poses)
+        vs_trace = k5_vs_trace(poses, frames, R, Cc, F, 11 + rank, a.warmup)
     # (a region never entered this run, e.g. rows_retree with host trees on,
     # reads as count 0)
     per_frame = lambda n: 1000.0 * kt[n][0] / kt[n][1] if kt[n][1] > 0 else 0.0
@@ -446,7 +509,7 @@ def run_k5(a, ws, rank, dev):
                      "Adam sums)" if a.k5_mode == "exact" else "frames carry the API's host "
                      "copies (global map slot, host trees)"))}
     out = {"metric": METRIC, "value": round(matches / elapsed, 1), "unit": "matches/s",
-           "n_gpus": ws, "steps": a.steps, "warmup": a.warmup,
+           "n_gpus": ws, "steps": a.steps, "warmup": a.warmup, "full": bool(a.full),
            "ms_per_step": round(1000.0 * elapsed / a.steps, 4), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f64",
            "data": (f"synthetic L9 stream: {F} ray-cast {R}x{Cc} frames along a walk "
@@ -467,9 +530,10 @@ def run_k5(a, ws, rank, dev):
            # the frame's API copies alone (the same pageable frame and map-slot
            # buffers, the same entry points, nothing else on the device): the
            # floor a frame of this API cannot go below
-           "copy_floor_ms": round(floor["ms"], 4),
+           "copy_floor_ms": round(floor["ms"], 4) if floor else None,
            "copy_floor": floor,
-           "frac_of_copy_floor": round(floor["ms"] / (1000.0 * elapsed / a.steps), 4),
+           "frac_of_copy_floor": (round(floor["ms"] / (1000.0 * elapsed / a.steps), 4)
+                                  if floor else None),
            "pose_vs_trace": vs_trace,
            "cpu_baseline": cpu}
     return out
@@ -665,6 +729,12 @@ def main():
             with torch.cuda.graph(graph, stream=stream):
                 g.pair_knn_dev(pairs_d[0][0], pairs_d[0][1], R, Cc, a.k, *outs[0])
             step = graph.replay  # noqa: F811
+
+        def last_outputs():
+            # what the last step's caller received: the output set of the
+            # context that step ran on (a captured graph always writes set 0)
+            j = 0 if (a.graph and nf == 1) else (turn[0] - 1) % nf
+            return dict(zip(("src_mask", "tgt_mask", "nn_idx", "nn_dist"), outs[j]))
         matches_per_step = N
         dom = "knn_query"
         dom_bytes = (24 + 24 + 12 * a.k) * N        # 24Q + 24T + 12kQ
@@ -727,6 +797,13 @@ def main():
                 g.rows_match_dev(srcs[0], tgts[0], R, Cc, sm[0], tm[0], idx[0], dst[0])
             if gather_buf is not None and do_gather[0]:
                 shard.gather_matches(packed, gather_buf)
+
+        def last_outputs():  # this rank's pairs (every step rewrites them all)
+            # nn_dist means something only where a match was found: inf elsewhere
+            found = idx[:pairs] >= 0
+            return {"src_mask": sm[:pairs], "tgt_mask": tm[:pairs], "nn_idx": idx[:pairs],
+                    "nn_dist": torch.where(found, dst[:pairs],
+                                           torch.full_like(dst[:pairs], float("inf")))}
         # matches = feature queries actually searched (constant per pair)
         step()
         torch.cuda.synchronize()
@@ -813,19 +890,22 @@ def main():
     elapsed = shard.max_over_ranks(t1 - t0, dev)
     job_matches = shard.sum_over_ranks(matches_per_step, dev)
     kt = timing_collect()
+    # before anything else runs on the contexts: the last timed step's outputs
+    if rank == 0 and a.dump_outputs and a.steps > 0:
+        dump_outputs(a.dump_outputs, {k: v.cpu().numpy() for k, v in last_outputs().items()})
     # isolated kernel durations: the same steps on one context alone, after
-    # the timed region (K3 with pairs in flight only)
+    # the timed region (K3 with pairs in flight only; --full)
     kt_iso = None
-    if iso_step is not None and nf > 1 and a.iso_steps > 0:
+    if a.full and iso_step is not None and nf > 1 and a.iso_steps > 0:
         g.timing_select(None)  # every region of the isolated steps
         for _ in range(a.iso_steps):
             iso_step()
         torch.cuda.synchronize()
         kt_iso = timing_collect()
     timing_on(False)
-    # K4 on N > 1 ranks: the same steps again without the all-gather
+    # K4 on N > 1 ranks: the same steps again without the all-gather (--full)
     no_gather = None
-    if a.workload in ("k2", "k4") and gather_buf is not None:
+    if a.full and a.workload in ("k2", "k4") and gather_buf is not None:
         do_gather[0] = False
         torch.cuda.synchronize()
         dist.barrier()
@@ -840,9 +920,10 @@ def main():
                      "ms_per_step": round(1000.0 * el2 / a.steps, 4),
                      "gather_bytes_per_rank": int(ws * packed.numel())}
     # measured HBM ceiling: a STREAM copy of 1 GiB, far above the
-    # 256 MiB Infinity Cache, on the library's stream (read + write bytes)
+    # 256 MiB Infinity Cache, on the library's stream (read + write bytes);
+    # --full
     stream_copy = None
-    if rank == 0 and not a.no_stream_copy:
+    if a.full and rank == 0 and not a.no_stream_copy:
         nb = 1 << 30
         sbuf = torch.empty(nb, dtype=torch.uint8, device=dev)
         dbuf = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -969,13 +1050,15 @@ def main():
                 path = dict(path or {}, isolated=path_of(kt_iso, f"{a.iso_steps} steps on one "
                                                         "context after the timed region"))
         cpu = None
-        if ws == 1 and not a.no_cpu_baseline and a.workload == "k3":
+        if not a.full:
+            pass  # the CPU baseline is a run of its own: --full
+        elif ws == 1 and not a.no_cpu_baseline and a.workload == "k3":
             cpu = cpu_baseline_k3(src_h, tgt_h, a.k, a.cpu_reps)
         elif rank == 0 and not a.no_cpu_baseline and a.workload in ("k2", "k4") and pairs:
             # one pair of the batch; the reference has no batching (K4 = pairs in turn)
             cpu = cpu_baseline_k2(srcs[0].cpu().numpy(), tgts[0].cpu().numpy(), a.cpu_reps)
         out = {"metric": METRIC, "value": round(value, 1), "unit": "matches/s",
-               "n_gpus": ws, "steps": a.steps, "warmup": a.warmup,
+               "n_gpus": ws, "steps": a.steps, "warmup": a.warmup, "full": bool(a.full),
                "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": data,
                "config": dict({"workload": workload, "parallelism": f"replicas x{ws}"},

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-bench_ab}; ROUNDS=${2:-3}; mkdir -p "$OUT"
 export NAVSLAM_QUIET=1
 for r in $(seq "$ROUNDS"); do
   for l in ${VDIR:-nav-slam_amd/lib/variants}/*.so; do
-    NAVGPU_LIB=$l timeout -k 10 120 python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline $BENCH_ARGS \
+    NAVGPU_LIB=$l timeout -k 10 120 python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline $BENCH_ARGS \
       --no-stream-copy --json-out "$OUT/b.json" > /dev/null 2>&1 || exit 1
     python3 - "$l" "$OUT/b.json" <<'PY'
 import json, os, sys

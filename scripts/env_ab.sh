@@ -5,7 +5,7 @@
 OUT=gpurun_out/$1; ROUNDS=$2; shift 2; mkdir -p "$OUT"
 for r in $(seq "$ROUNDS"); do
   for v in "$@"; do
-    env $v timeout -k 10 120 python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline \
+    env $v timeout -k 10 120 python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline \
       --no-stream-copy ${BENCH_ARGS} --json-out "$OUT/b.json" > "$OUT/b.log" 2>&1 || { tail -20 "$OUT/b.log"; exit 1; }
     python3 - "$v" "$OUT/b.json" <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ for r in $(seq 1 "$ROUNDS"); do
     label=${spec%%:*}; rest=${spec#*:}
     envs=${rest%%@*}; args=""; [ "$rest" != "$envs" ] && args=${rest#*@}
     f="$OUT/${label}_$r.json"
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-stream-copy $BENCH_ARGS $args --json-out "$f" > "$OUT/${label}_$r.log" 2>&1
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-stream-copy $BENCH_ARGS $args --json-out "$f" > "$OUT/${label}_$r.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$label round $r rc=$rc"; tail -5 "$OUT/${label}_$r.log"; exit $rc; fi
     python3 scripts/k3_line_summary.py "$label" "$f"

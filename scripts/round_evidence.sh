@@ -29,7 +29,7 @@ if [ -z "$SKIP_TESTS" ] && part tests; then
   step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
 fi
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-traffic-json --no-stream-copy"
+Q="--full --no-cpu-baseline --no-traffic-json --no-stream-copy"
 if part k3; then
 step trace_k3 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_k3" -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 $Q --json-out "$OUT/bench_k3_traced.json"
 # one pair at a time: the trace's per-launch kernel sums and the line's HIP
@@ -66,16 +66,16 @@ fi
 if part bench; then
 # a traffic json made earlier in this session, else the committed one
 tj() { if [ -f "$OUT/traffic_$1.json" ]; then echo "$OUT/traffic_$1.json"; else echo "profiles/traffic_$1.json"; fi; }
-step bench_k3 600 python3 bench.py --traffic-json "$(tj k3)" --json-out "$OUT/bench_k3.json"
-step bench_k3_inflight1 300 python3 bench.py --inflight 1 --no-cpu-baseline --traffic-json "$(tj k3)" --json-out "$OUT/bench_k3_inflight1.json"
-step bench_k2 300 python3 bench.py --workload k2 --steps 100 --traffic-json "$(tj k2)" --json-out "$OUT/bench_k2.json"
-step bench_k2i 300 python3 bench.py --workload k2 --integer-mm --steps 100 --traffic-json "$(tj k2i)" --json-out "$OUT/bench_k2i.json"
-step bench_k4 400 python3 bench.py --workload k4 --steps 10 --warmup 2 --traffic-json "$(tj k4)" --json-out "$OUT/bench_k4.json"
-step bench_k4i 400 python3 bench.py --workload k4 --integer-mm --steps 10 --warmup 2 --traffic-json "$(tj k4i)" --json-out "$OUT/bench_k4i.json"
-step bench_k5 400 python3 bench.py --workload k5 --steps 30 --warmup 2 --json-out "$OUT/bench_k5.json"
-step bench_k5_fast 400 python3 bench.py --workload k5 --k5-mode fast --steps 30 --warmup 2 --traffic-json "$(tj k5f)" --json-out "$OUT/bench_k5_fast.json"
-NAVSLAM_HOST_TREES=0 step bench_k5_fast_lazy 400 python3 bench.py --workload k5 --k5-mode fast --steps 300 --warmup 10 --traffic-json "$(tj k5fl)" --json-out "$OUT/bench_k5_fast_lazy.json"
-NAVSLAM_HOST_TREES=0 step bench_k5_fast_lazy_10k 600 python3 bench.py --workload k5 --k5-mode fast --steps 9990 --warmup 10 --traffic-json "$(tj k5fl)" --no-cpu-baseline --json-out "$OUT/bench_k5_fast_lazy_10k.json"
-step trace_k5 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace_k5" -o run --output-format csv -- python3 bench.py --workload k5 --k5-mode fast --steps 20 --warmup 2 --no-cpu-baseline --no-traffic-json
+step bench_k3 600 python3 bench.py --full --traffic-json "$(tj k3)" --json-out "$OUT/bench_k3.json"
+step bench_k3_inflight1 300 python3 bench.py --full --inflight 1 --no-cpu-baseline --traffic-json "$(tj k3)" --json-out "$OUT/bench_k3_inflight1.json"
+step bench_k2 300 python3 bench.py --full --workload k2 --steps 100 --traffic-json "$(tj k2)" --json-out "$OUT/bench_k2.json"
+step bench_k2i 300 python3 bench.py --full --workload k2 --integer-mm --steps 100 --traffic-json "$(tj k2i)" --json-out "$OUT/bench_k2i.json"
+step bench_k4 400 python3 bench.py --full --workload k4 --steps 10 --warmup 2 --traffic-json "$(tj k4)" --json-out "$OUT/bench_k4.json"
+step bench_k4i 400 python3 bench.py --full --workload k4 --integer-mm --steps 10 --warmup 2 --traffic-json "$(tj k4i)" --json-out "$OUT/bench_k4i.json"
+step bench_k5 400 python3 bench.py --full --workload k5 --steps 30 --warmup 2 --json-out "$OUT/bench_k5.json"
+step bench_k5_fast 400 python3 bench.py --full --workload k5 --k5-mode fast --steps 30 --warmup 2 --traffic-json "$(tj k5f)" --json-out "$OUT/bench_k5_fast.json"
+NAVSLAM_HOST_TREES=0 step bench_k5_fast_lazy 400 python3 bench.py --full --workload k5 --k5-mode fast --steps 300 --warmup 10 --traffic-json "$(tj k5fl)" --json-out "$OUT/bench_k5_fast_lazy.json"
+NAVSLAM_HOST_TREES=0 step bench_k5_fast_lazy_10k 600 python3 bench.py --full --workload k5 --k5-mode fast --steps 9990 --warmup 10 --traffic-json "$(tj k5fl)" --no-cpu-baseline --json-out "$OUT/bench_k5_fast_lazy_10k.json"
+step trace_k5 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace_k5" -o run --output-format csv -- python3 bench.py --full --workload k5 --k5-mode fast --steps 20 --warmup 2 --no-cpu-baseline --no-traffic-json
 fi
 echo done

@@ -91,3 +91,48 @@ def test_traffic_tags(monkeypatch):
     with open(os.path.join(ROOT, "profiles", "traffic_k3.json")) as fh:
         tj = json.load(fh)
     assert tj["k"] == 8 and tj["points_per_cloud"] == 1048576 and tj["bytes_per_step"] > 0
+
+
+def test_dump_outputs_formats_budget_and_sample(tmp_path):
+    """--dump-outputs: float32 / float64 files within the byte budget; an
+    array above its share is a row sample that is the same from run to run
+    and draws whole rows of the array, in order."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    arrays = {"mask": rng.integers(0, 2, (16, 64)).astype(np.int32),
+              "idx": rng.integers(-1, 1 << 20, (1024, 8)).astype(np.int32),
+              "big": np.array([[-1, (1 << 24) + 1]], np.int32),   # not exact in float32
+              "dist": rng.random((1024, 8))}
+    budget = 40000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert sum(v.nbytes for v in got.values()) <= budget
+    assert got["mask"].dtype == np.float32 and got["idx"].dtype == np.float32
+    assert got["big"].dtype == np.float64 and got["dist"].dtype == np.float64
+    np.testing.assert_array_equal(got["mask"], arrays["mask"])
+    np.testing.assert_array_equal(got["big"], arrays["big"])
+    for n in ("idx", "dist"):   # sampled: whole rows of the source, ascending
+        v = got[n]
+        assert v.ndim == 2 and v.shape[1] == 8 and 0 < v.shape[0] < 1024
+        src = arrays[n].astype(v.dtype)
+        pos = [int(np.flatnonzero((src == row).all(axis=1))[0]) for row in v]
+        assert pos == sorted(pos) and len(set(pos)) == len(pos)
+    for n in arrays:
+        np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+    # everything fits: nothing is sampled
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "dist.npy"), arrays["dist"])
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        plain = bench.parse()
+        sys.argv = sys.argv + ["--full", "--dump-outputs", "d"]
+        full = bench.parse()
+    finally:
+        sys.argv = old
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 3
+    assert full.full is True and full.dump_outputs == "d"
