@@ -32,6 +32,8 @@
  *                          have a distance tie)
  *   navgpu_knn_*           global-mode k-NN (the reference has k = 1 only;
  *                          ordering = (distance, index))
+ *   navgpu_align_*, navgpu_icp_*  none: a 6-DOF rigid fit on the k-NN's
+ *                          output (the reference registers no rotation)
  */
 #ifndef NAVGPU_H
 #define NAVGPU_H
@@ -240,6 +242,66 @@ int navgpu_knn_host(navgpu_ctx *ctx, const double *tgt, size_t nt,
 int navgpu_pair_knn_dev(navgpu_ctx *ctx, const double *src, const double *tgt,
                         int R, int C, int k, int32_t *src_mask,
                         int32_t *tgt_mask, int32_t *idx, double *dist);
+
+/* ---- 6-DOF rigid registration on the global k-NN -------------------------
+ * Not part of the reference interface: its optimiser fits a translation only
+ * (src/slam.c:300-389). DESIGN.md §10.
+ *
+ * navgpu_align_*: one align step. idx / dist are rows of `stride` (1..16)
+ * entries per query as navgpu_knn_* writes them with k = stride; only slot 0
+ * is read. Query q is a pair (p = src[q], nearest = tgt[j]), j = idx[q*stride],
+ * when 0 <= j < nt, dist[q*stride] <= max_dist (a NaN distance fails;
+ * max_dist = +INFINITY is no gate; a NaN max_dist is NAVGPU_EINVAL) and
+ * mask == NULL or mask[q] != 0. A j outside [-1, nt) is rejected like the
+ * rest, counted in stats[3] and never dereferenced. delta (12 doubles)
+ * receives the least-squares rigid motion of the pairs, R row-major then t
+ * (the Rm / t of navgpu_transform_dev: nearest ~ t + R p), by Horn's closed
+ * form over moments centred in a second pass, so the fit is exact at any
+ * coordinate magnitude. With fewer than 3 pairs delta is the identity.
+ * pose (12 doubles, nullable) is replaced by delta o pose (R' = dR R,
+ * t' = dR t + dt). stats (4 doubles): pairs n; rms |nearest - p| over them;
+ * the rms after the step, sqrt(max(0, Spp + Sqq - 2 sum_ij R_ij H_ji) / n)
+ * from the centred moments (= the rms before when n < 3); the count of
+ * indices outside [-1, nt). nq == 0 is a clean call that gives the identity.
+ * The sums use no floating-point atomics and a launch shape that depends on
+ * nq alone: the same input gives the same bits on every run. Timed as
+ * "align". */
+int navgpu_align_dev(navgpu_ctx *ctx, const double *src, size_t nq,
+                     const double *tgt, size_t nt, const int32_t *idx,
+                     const double *dist, int stride, double max_dist,
+                     const int32_t *mask, double *delta, double *pose,
+                     double *stats);
+/* The same on host pointers (Rm[9], t[3], stats[4] on the host). */
+int navgpu_align_host(navgpu_ctx *ctx, const double *src, size_t nq,
+                      const double *tgt, size_t nt, const int32_t *idx,
+                      const double *dist, int stride, double max_dist,
+                      const int32_t *mask, double Rm[9], double t[3],
+                      double stats[4]);
+
+/* navgpu_transform_dev with the pose (R row-major then t, 12 doubles) read
+ * from DEVICE memory: out = t + R p in the same operation order, so a pose
+ * made on the device is applied without a host round trip. */
+int navgpu_transform_pose_dev(navgpu_ctx *ctx, const double *pts, size_t n,
+                              const double *pose_dev, double *out);
+
+/* Point-to-point ICP, `iters` (1..64) iterations, each: cur = pose(src);
+ * navgpu_knn_dev(tgt, cur, k = 1); the align step on cur; pose <- delta o
+ * pose, hist[i] = pose and stats[i] recorded (both nullable; stats rows as
+ * above). pose (12 doubles) is the start on entry and the result on return.
+ * The iteration count is fixed: early exit is the caller's, from stats. The
+ * target's grid index is rebuilt by every iteration's k-NN call. The time
+ * splits into the regions "icp_transform", "knn_build", "knn_query" and
+ * "align". navgpu_knn_check reports on the last iteration's k-NN. */
+int navgpu_icp_dev(navgpu_ctx *ctx, const double *src, size_t nq,
+                   const double *tgt, size_t nt, int iters, double max_dist,
+                   const int32_t *mask, double *pose, double *hist,
+                   double *stats);
+/* The same on host pointers: pose[12] in/out, hist[iters][12] and
+ * stats[iters][4] nullable; checks navgpu_knn_check itself. */
+int navgpu_icp_host(navgpu_ctx *ctx, const double *src, size_t nq,
+                    const double *tgt, size_t nt, int iters, double max_dist,
+                    const int32_t *mask, double pose[12], double *hist,
+                    double *stats);
 
 /* ---- R5 for one arbitrary point array (kdtree.h buildKDTree) ------------
  * pts: n points (AoS), permuted in place into the reference's buildKDTree

@@ -1,6 +1,7 @@
-// navgpu_common.h — what the two translation units of libnavgpu.so share:
-// navgpu.hip (per-row mode, curvature, KD build, host plumbing) and knn.hip
-// (global-mode grid index and exact k-NN). Internal: never installed.
+// navgpu_common.h — what the three translation units of libnavgpu.so share:
+// navgpu.hip (per-row mode, curvature, KD build, host plumbing), knn.hip
+// (global-mode grid index and exact k-NN) and align.hip (rigid registration
+// on the k-NN's output). Internal: never installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -244,6 +245,7 @@ enum Slot {
   kKdFc, kKdP, kKdT, kQStart, kQCell, kQSlot, kQPerm, kStats, kOvf, kSlowQ,
   kSlowThr, kTSort, kRowMaskS, kRowMaskT, kRowTie, kCorrEnt, kCorrN, kCorrSums, kKdPtmp, kKdSel,
   kQSort, kCellId2, kSRec, kNpg, kGl, kRowTieLazy,
+  kAlignPart, kAlignOut, kIcpCur, kIcpIdx, kIcpDist,  // align.hip
   kH0 = 100, kH1, kH2, kH3, kH4, kH5,
 };
 

@@ -66,6 +66,15 @@ def _declare(L):
         "navgpu_knn_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_int, _vp, _vp]),
         "navgpu_pair_knn_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                           _vp, _vp, _vp, _vp]),
+        "navgpu_align_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int, C.c_double,
+                                       _vp, _vp, _vp, _vp]),
+        "navgpu_align_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int, C.c_double,
+                                        _vp, _vp, _vp, _vp]),
+        "navgpu_transform_pose_dev": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+        "navgpu_icp_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp,
+                                     _vp, _vp]),
+        "navgpu_icp_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp,
+                                      _vp, _vp]),
         "navgpu_kd_build_dev": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_kd_build_host": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_malloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
@@ -259,6 +268,51 @@ class NavGpu:
                                            _ptr(idx), _ptr(dist)), "knn")
         return idx, dist
 
+    def align(self, src, tgt, idx, dist, max_dist=np.inf, mask=None):
+        """One 6-DOF align step on the pairs (src[q], tgt[idx[q, 0]]) that pass
+        the gate (navgpu.h): (R[3,3], t[3], stats[4]) with tgt ~ t + R src."""
+        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
+        nq = len(src)
+        # rows of k slots per query as knn() returns them (an empty call has none)
+        idx = np.ascontiguousarray(idx, np.int32).reshape((nq, -1) if nq else (0, 1))
+        dist = np.ascontiguousarray(dist, np.float64).reshape((nq, -1) if nq else (0, 1))
+        if idx.shape != dist.shape:
+            raise ValueError("align: idx and dist differ in shape")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
+            if len(mask) != nq:
+                raise ValueError("align: one mask entry per query")
+        stride = idx.shape[1]
+        R, t, stats = np.zeros((3, 3)), np.zeros(3), np.zeros(4)
+        self._check(self.L.navgpu_align_host(
+            self.h, _ptr(src), nq, _ptr(tgt), len(tgt), _ptr(idx), _ptr(dist), stride,
+            float(max_dist), _ptr(mask), _ptr(R), _ptr(t), _ptr(stats)), "align")
+        return R, t, stats
+
+    def icp(self, src, tgt, iters=10, max_dist=np.inf, mask=None, init=None):
+        """Point-to-point ICP of src onto tgt, a fixed `iters` iterations from
+        the pose init = (R, t) (default: the identity):
+        (R[3,3], t[3], stats[iters,4], hist[iters,12])."""
+        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
+            if len(mask) != len(src):
+                raise ValueError("icp: one mask entry per source point")
+        pose = np.zeros(12)
+        if init is None:
+            pose[[0, 4, 8]] = 1.0
+        else:
+            pose[:9] = np.asarray(init[0], np.float64).reshape(9)
+            pose[9:] = np.asarray(init[1], np.float64).reshape(3)
+        hist = np.zeros((iters, 12))
+        stats = np.zeros((iters, 4))
+        self._check(self.L.navgpu_icp_host(
+            self.h, _ptr(src), len(src), _ptr(tgt), len(tgt), iters, float(max_dist),
+            _ptr(mask), _ptr(pose), _ptr(hist), _ptr(stats)), "icp")
+        return pose[:9].reshape(3, 3).copy(), pose[9:].copy(), stats, hist
+
     def kd_build(self, pts, depth0=0):
         """Reference buildKDTree permutation of `pts` (returns a new array)."""
         p = np.array(pts, np.float64, order="C").reshape(-1, 3)
@@ -278,6 +332,22 @@ class NavGpu:
         self._check(self.L.navgpu_transform_dev(self.h, _ptr(pts), n, _ptr(Rm), _ptr(t),
                                                 _ptr(tr), _ptr(out), _ptr(out_last)),
                     "transform_dev")
+
+    def align_dev(self, src, nq, tgt, nt, idx, dist, stride, max_dist, mask, delta, pose,
+                  stats):
+        self._check(self.L.navgpu_align_dev(
+            self.h, _ptr(src), nq, _ptr(tgt), nt, _ptr(idx), _ptr(dist), stride,
+            float(max_dist), _ptr(mask), _ptr(delta), _ptr(pose), _ptr(stats)), "align_dev")
+
+    def transform_pose_dev(self, pts, n, pose, out):
+        """transform_dev with the 12-double pose (R row-major, then t) on the device."""
+        self._check(self.L.navgpu_transform_pose_dev(self.h, _ptr(pts), n, _ptr(pose),
+                                                     _ptr(out)), "transform_pose_dev")
+
+    def icp_dev(self, src, nq, tgt, nt, iters, max_dist, mask, pose, hist=None, stats=None):
+        self._check(self.L.navgpu_icp_dev(
+            self.h, _ptr(src), nq, _ptr(tgt), nt, iters, float(max_dist), _ptr(mask),
+            _ptr(pose), _ptr(hist), _ptr(stats)), "icp_dev")
 
     def kd_build_dev(self, pts, n, depth0=0):
         self._check(self.L.navgpu_kd_build_dev(self.h, _ptr(pts), n, depth0), "kd_build_dev")
