@@ -34,6 +34,9 @@
  *                          ordering = (distance, index))
  *   navgpu_align_*, navgpu_icp_*  none: a 6-DOF rigid fit on the k-NN's
  *                          output (the reference registers no rotation)
+ *   navgpu_normals_*, navgpu_cloud_normals_*, navgpu_align_plane_*,
+ *   navgpu_icp_plane_*     none: surface normals from the k-NN's rows and
+ *                          the point-to-plane fit on them
  */
 #ifndef NAVGPU_H
 #define NAVGPU_H
@@ -302,6 +305,101 @@ int navgpu_icp_host(navgpu_ctx *ctx, const double *src, size_t nq,
                     const double *tgt, size_t nt, int iters, double max_dist,
                     const int32_t *mask, double pose[12], double *hist,
                     double *stats);
+
+/* ---- Point-to-plane registration: normals, align step, ICP ----------------
+ * Not part of the reference interface. DESIGN.md §11.
+ *
+ * navgpu_normals_*: a unit surface normal and a curvature for each of the n
+ * points of pts from its neighbourhood. idx holds rows of `stride` entries
+ * per point as navgpu_knn_* writes them; the first k are read
+ * (3 <= k <= stride <= 16). A slot outside [0, n) is skipped and never
+ * dereferenced. With m valid slots, mu = sum x / m and the centred covariance
+ * C = sum (x - mu)(x - mu)^T have the eigenvalues l0 <= l1 <= l2 (cyclic
+ * Jacobi): normals[3 i ..] is the unit eigenvector of l0 and curv[i]
+ * (nullable) = max(l0, 0) / (l0 + l1 + l2). A point with m < 3, l2 <= 0 or
+ * l1 <= 1e-12 l2 (coincident or collinear neighbours: no plane) gets the
+ * normal (0, 0, 0) and the curvature NaN. Orientation: with a viewpoint
+ * (3 HOST doubles, nullable) the normal is flipped when n . (vp - p_i) < 0;
+ * without one its component of largest magnitude (lowest index on ties) is
+ * made positive. Timed as "normals".
+ * navgpu_cloud_normals_*: navgpu_knn_dev(pts, pts, k) into the workspace,
+ * then the above on its rows as written (a point is its own slot 0 unless a
+ * coincident point has a lower index). */
+int navgpu_normals_dev(navgpu_ctx *ctx, const double *pts, size_t n,
+                       const int32_t *idx, int stride, int k,
+                       const double *viewpoint, double *normals, double *curv);
+int navgpu_normals_host(navgpu_ctx *ctx, const double *pts, size_t n,
+                        const int32_t *idx, int stride, int k,
+                        const double *viewpoint, double *normals, double *curv);
+int navgpu_cloud_normals_dev(navgpu_ctx *ctx, const double *pts, size_t n,
+                             int k, const double *viewpoint, double *normals,
+                             double *curv);
+/* On host pointers; checks navgpu_knn_check itself. */
+int navgpu_cloud_normals_host(navgpu_ctx *ctx, const double *pts, size_t n,
+                              int k, const double *viewpoint, double *normals,
+                              double *curv);
+
+/* navgpu_align_plane_*: one point-to-plane step. The gate is
+ * navgpu_align_dev's (slot 0 of each row, 0 <= j < nt, dist <= max_dist, mask)
+ * and tgt_curv[j] <= max_curv: a NaN curvature (no normal at j) fails it, so
+ * max_curv = +INFINITY admits every valid normal. A NaN max_dist or max_curv
+ * is NAVGPU_EINVAL. With x = p - pbar (pbar the centroid of the accepted
+ * source points), n = tgt_normals[j] and r = (tgt[j] - p) . n, the step
+ * minimises sum (r - [x cross n, n] . (omega, tau))^2 by the 6 x 6 normal
+ * equations scaled to unit diagonal and factored without pivoting; delta (12
+ * doubles) is R row-major, the Cayley rotation of omega (the unit quaternion
+ * of (1, omega / 2)), then t = tau + pbar - R pbar. The step is refused, delta
+ * the identity, with fewer than 6 pairs, a diagonal entry <= 0 or a pivot
+ * <= 1e-10 (parallel normals). pose (12 doubles, nullable) is replaced by
+ * delta o pose as in navgpu_align_dev. stats (6 doubles): pairs n; rms of r;
+ * the linear model's rms after the step (= the rms before when refused);
+ * indices outside [-1, nt); 1 if solved, 0 if refused; the smallest pivot
+ * (0 when refused before the factorisation). nq == 0 is a clean call that
+ * gives the identity. Reproducible bit for bit like navgpu_align_dev. Timed
+ * as "align_plane". */
+int navgpu_align_plane_dev(navgpu_ctx *ctx, const double *src, size_t nq,
+                           const double *tgt, size_t nt,
+                           const double *tgt_normals, const double *tgt_curv,
+                           const int32_t *idx, const double *dist, int stride,
+                           double max_dist, double max_curv,
+                           const int32_t *mask, double *delta, double *pose,
+                           double *stats);
+/* The same on host pointers (Rm[9], t[3], stats[6] on the host). */
+int navgpu_align_plane_host(navgpu_ctx *ctx, const double *src, size_t nq,
+                            const double *tgt, size_t nt,
+                            const double *tgt_normals, const double *tgt_curv,
+                            const int32_t *idx, const double *dist, int stride,
+                            double max_dist, double max_curv,
+                            const int32_t *mask, double Rm[9], double t[3],
+                            double stats[6]);
+
+/* Point-to-plane ICP: navgpu_icp_dev's loop (cur = pose(src);
+ * navgpu_knn_dev(tgt, cur, k = 1); the step; pose <- delta o pose) with the
+ * plane step on the target's normals. hist[iters][12] and stats[iters][6]
+ * nullable. No host synchronisation and, once the workspace is warm, no
+ * allocation. */
+int navgpu_icp_plane_dev(navgpu_ctx *ctx, const double *src, size_t nq,
+                         const double *tgt, size_t nt,
+                         const double *tgt_normals, const double *tgt_curv,
+                         int iters, double max_dist, double max_curv,
+                         const int32_t *mask, double *pose, double *hist,
+                         double *stats);
+/* On host pointers: the target's normals are computed once, as
+ * navgpu_cloud_normals_dev(tgt, kn, viewpoint) does, then the loop runs.
+ * Checks navgpu_knn_check itself. */
+int navgpu_icp_plane_host(navgpu_ctx *ctx, const double *src, size_t nq,
+                          const double *tgt, size_t nt, int kn,
+                          const double *viewpoint, int iters, double max_dist,
+                          double max_curv, const int32_t *mask,
+                          double pose[12], double *hist, double *stats);
+/* On host pointers with the target's normals and curvatures given. */
+int navgpu_icp_plane_normals_host(navgpu_ctx *ctx, const double *src,
+                                  size_t nq, const double *tgt, size_t nt,
+                                  const double *tgt_normals,
+                                  const double *tgt_curv, int iters,
+                                  double max_dist, double max_curv,
+                                  const int32_t *mask, double pose[12],
+                                  double *hist, double *stats);
 
 /* ---- R5 for one arbitrary point array (kdtree.h buildKDTree) ------------
  * pts: n points (AoS), permuted in place into the reference's buildKDTree

@@ -15,16 +15,18 @@
 // Sums are reproducible bit for bit: per-thread f64 accumulators over a
 // grid-stride loop, a fixed butterfly per wave, the waves of a block added in
 // wave order, one partial row per block, the rows added in a fixed order. The
-// grid is a function of nq alone. There are no floating-point atomics.
+// grid is a function of nq alone. There are no floating-point atomics. The
+// helpers are in det_reduce.h, shared with plane.hip.
 #include "navgpu_common.h"
 
 #include "align_solve.h"
+#include "det_reduce.h"
 
 using namespace nv;
 
 namespace {
 
-constexpr int kAlignBlock = 256;  // 4 waves, one per SIMD
+constexpr int kAlignBlock = kRedBlock;  // 4 waves, one per SIMD
 // Independent queries in flight per lane: the 24-B target gather is a random
 // access, so each lane issues kAlignU of them before it consumes the first.
 constexpr int kAlignU = 4;
@@ -33,7 +35,6 @@ constexpr int kAlignMaxGrid = 1024;  // 4 blocks (16 waves) on each of the 256 C
 constexpr int kAlignRow = 16;        // doubles per partial row (128 B)
 constexpr int kNA = 9;               // pass A: n, sum p, sum q, sum |q-p|^2, bad
 constexpr int kNB = 11;              // pass B: H, Spp, Sqq
-constexpr int kAlignWaves = kAlignBlock / kWave;
 
 struct AlignIn {
   const double *src, *tgt;  // tgt is never null here (align_run substitutes)
@@ -44,32 +45,6 @@ struct AlignIn {
   int nt, stride;
   double max_dist;
 };
-
-// all 64 lanes end with the same sum, added in the same order every run
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// the block's sum of each of acc[0..NV): out[k] (LDS or global) by thread k
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&acc)[NV], double *out) {
-  __shared__ double sh[kAlignWaves][NV];
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) acc[k] = wave_sum(acc[k]);
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) sh[wid][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double s = sh[0][threadIdx.x];
-    for (int w = 1; w < kAlignWaves; ++w) s += sh[w][threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-}
 
 // One pass over the queries. A query is accepted when its slot-0 neighbour j
 // is a target index, its distance passes the gate (a NaN fails `<=`) and its
@@ -163,27 +138,11 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_moments(AlignIn a,
   block_sum<NV>(acc, part + (size_t)blockIdx.x * kAlignRow);
 }
 
-// the sum over the nblk partial rows, in a fixed order: thread t adds rows
-// t, t + 256, ... ascending, then the block's fixed tree; out: LDS, NV doubles
-template <int NV>
-__device__ __forceinline__ void combine_rows(const double *__restrict__ part, int nblk,
-                                             double *out) {
-  double acc[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-  for (int r = threadIdx.x; r < nblk; r += kAlignBlock) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc[k] += part[(size_t)r * kAlignRow + k];
-  }
-  block_sum<NV>(acc, out);
-  __syncthreads();
-}
-
 // cent = n, pbar, qbar, sum |q-p|^2, bad indices
 __global__ __launch_bounds__(kAlignBlock) void k_align_finish(const double *__restrict__ partA,
                                                               int nblk, double *__restrict__ cent) {
   __shared__ double o[kNA];
-  combine_rows<kNA>(partA, nblk, o);
+  combine_rows<kNA, kAlignRow>(partA, nblk, o);
   if (threadIdx.x == 0) {
     const double n = o[0];
     cent[0] = n;
@@ -203,7 +162,7 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_solve(const double *__res
                                                              double *__restrict__ stats,
                                                              double *pose, double *hist) {
   __shared__ double o[kNB];
-  combine_rows<kNB>(partB, nblk, o);
+  combine_rows<kNB, kAlignRow>(partB, nblk, o);
   if (threadIdx.x != 0) return;
   double m[kAlignMoments], d[12], st[4];
   for (int i = 0; i < 8; ++i) m[i] = cent[i];
@@ -242,7 +201,7 @@ __global__ __launch_bounds__(256) void k_transform_pose(const double *__restrict
 constexpr size_t kAlignPartDoubles = 2 * (size_t)kAlignMaxGrid * kAlignRow + kAlignRow;
 
 unsigned align_grid(size_t nq) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(kAlignMaxGrid, (nq + kAlignTile - 1) / kAlignTile));
+  return det_grid(nq, kAlignTile, kAlignMaxGrid);
 }
 
 // The align step on device pointers; hist (nullable) also receives the

@@ -1,7 +1,8 @@
-// navgpu_common.h — what the three translation units of libnavgpu.so share:
+// navgpu_common.h — what the four translation units of libnavgpu.so share:
 // navgpu.hip (per-row mode, curvature, KD build, host plumbing), knn.hip
-// (global-mode grid index and exact k-NN) and align.hip (rigid registration
-// on the k-NN's output). Internal: never installed.
+// (global-mode grid index and exact k-NN), align.hip (rigid registration
+// on the k-NN's output) and plane.hip (surface normals and point-to-plane
+// registration on it). Internal: never installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -246,6 +247,7 @@ enum Slot {
   kSlowThr, kTSort, kRowMaskS, kRowMaskT, kRowTie, kCorrEnt, kCorrN, kCorrSums, kKdPtmp, kKdSel,
   kQSort, kCellId2, kSRec, kNpg, kGl, kRowTieLazy,
   kAlignPart, kAlignOut, kIcpCur, kIcpIdx, kIcpDist,  // align.hip
+  kPlanePart, kPlaneOut, kNormIdx, kNormDist, kPlaneNrm, kPlaneCurv,  // plane.hip
   kH0 = 100, kH1, kH2, kH3, kH4, kH5,
 };
 

@@ -75,6 +75,23 @@ def _declare(L):
                                      _vp, _vp]),
         "navgpu_icp_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_int, C.c_double, _vp, _vp,
                                       _vp, _vp]),
+        "navgpu_normals_dev": (C.c_int, [_vp, _vp, _sz, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+        "navgpu_normals_host": (C.c_int, [_vp, _vp, _sz, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+        "navgpu_cloud_normals_dev": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp, _vp]),
+        "navgpu_cloud_normals_host": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp, _vp]),
+        "navgpu_align_plane_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp,
+                                             C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
+                                             _vp]),
+        "navgpu_align_plane_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp,
+                                              C.c_int, C.c_double, C.c_double, _vp, _vp, _vp,
+                                              _vp]),
+        "navgpu_icp_plane_dev": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int,
+                                           C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+        "navgpu_icp_plane_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, C.c_int, _vp, C.c_int,
+                                            C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+        "navgpu_icp_plane_normals_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int,
+                                                    C.c_double, C.c_double, _vp, _vp, _vp,
+                                                    _vp]),
         "navgpu_kd_build_dev": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_kd_build_host": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_malloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
@@ -313,6 +330,99 @@ class NavGpu:
             _ptr(mask), _ptr(pose), _ptr(hist), _ptr(stats)), "icp")
         return pose[:9].reshape(3, 3).copy(), pose[9:].copy(), stats, hist
 
+    @staticmethod
+    def _viewpoint(viewpoint):
+        if viewpoint is None:
+            return None
+        return np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+
+    def normals(self, pts, k=8, viewpoint=None, idx=None):
+        """Surface normals and curvatures of a cloud (navgpu.h): (normals[n,3],
+        curv[n]). Neighbourhoods: the first k slots of the rows idx[n, stride]
+        when given, else the cloud's own k-NN. A point without a plane gets the
+        normal 0 and the curvature NaN."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        n = len(pts)
+        vp = self._viewpoint(viewpoint)
+        nrm, curv = np.zeros((n, 3)), np.zeros(n)
+        if idx is None:
+            self._check(self.L.navgpu_cloud_normals_host(
+                self.h, _ptr(pts), n, k, _ptr(vp), _ptr(nrm), _ptr(curv)), "normals")
+        else:
+            idx = np.ascontiguousarray(idx, np.int32)
+            if idx.ndim != 2 or len(idx) != n:
+                raise ValueError("normals: idx is one row of neighbours per point")
+            self._check(self.L.navgpu_normals_host(
+                self.h, _ptr(pts), n, _ptr(idx), idx.shape[1], k, _ptr(vp), _ptr(nrm),
+                _ptr(curv)), "normals")
+        return nrm, curv
+
+    def align_plane(self, src, tgt, tgt_normals, tgt_curv, idx, dist, max_dist=np.inf,
+                    max_curv=np.inf, mask=None):
+        """One point-to-plane step on the pairs (src[q], tgt[idx[q, 0]]) that
+        pass the gate (navgpu.h): (R[3,3], t[3], stats[6])."""
+        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
+        tn = np.ascontiguousarray(tgt_normals, np.float64).reshape(-1, 3)
+        tc = np.ascontiguousarray(tgt_curv, np.float64).reshape(-1)
+        if len(tn) != len(tgt) or len(tc) != len(tgt):
+            raise ValueError("align_plane: one normal and one curvature per target point")
+        nq = len(src)
+        idx = np.ascontiguousarray(idx, np.int32).reshape((nq, -1) if nq else (0, 1))
+        dist = np.ascontiguousarray(dist, np.float64).reshape((nq, -1) if nq else (0, 1))
+        if idx.shape != dist.shape:
+            raise ValueError("align_plane: idx and dist differ in shape")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
+            if len(mask) != nq:
+                raise ValueError("align_plane: one mask entry per query")
+        R, t, stats = np.zeros((3, 3)), np.zeros(3), np.zeros(6)
+        self._check(self.L.navgpu_align_plane_host(
+            self.h, _ptr(src), nq, _ptr(tgt), len(tgt), _ptr(tn), _ptr(tc), _ptr(idx),
+            _ptr(dist), idx.shape[1], float(max_dist), float(max_curv), _ptr(mask), _ptr(R),
+            _ptr(t), _ptr(stats)), "align_plane")
+        return R, t, stats
+
+    def icp_plane(self, src, tgt, tgt_normals=None, tgt_curv=None, iters=10, max_dist=np.inf,
+                  max_curv=np.inf, mask=None, init=None, kn=8, viewpoint=None):
+        """Point-to-plane ICP of src onto tgt, a fixed `iters` iterations from
+        the pose init = (R, t) (default: the identity). The target's normals
+        and curvatures are the given ones, or computed once from its kn-NN and
+        `viewpoint` as normals() does:
+        (R[3,3], t[3], stats[iters,6], hist[iters,12])."""
+        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
+            if len(mask) != len(src):
+                raise ValueError("icp_plane: one mask entry per source point")
+        if (tgt_normals is None) != (tgt_curv is None):
+            raise ValueError("icp_plane: give both tgt_normals and tgt_curv, or neither")
+        pose = np.zeros(12)
+        if init is None:
+            pose[[0, 4, 8]] = 1.0
+        else:
+            pose[:9] = np.asarray(init[0], np.float64).reshape(9)
+            pose[9:] = np.asarray(init[1], np.float64).reshape(3)
+        hist = np.zeros((iters, 12))
+        stats = np.zeros((iters, 6))
+        if tgt_normals is None:
+            vp = self._viewpoint(viewpoint)
+            self._check(self.L.navgpu_icp_plane_host(
+                self.h, _ptr(src), len(src), _ptr(tgt), len(tgt), kn, _ptr(vp), iters,
+                float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist),
+                _ptr(stats)), "icp_plane")
+        else:
+            tn = np.ascontiguousarray(tgt_normals, np.float64).reshape(-1, 3)
+            tc = np.ascontiguousarray(tgt_curv, np.float64).reshape(-1)
+            if len(tn) != len(tgt) or len(tc) != len(tgt):
+                raise ValueError("icp_plane: one normal and one curvature per target point")
+            self._check(self.L.navgpu_icp_plane_normals_host(
+                self.h, _ptr(src), len(src), _ptr(tgt), len(tgt), _ptr(tn), _ptr(tc), iters,
+                float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist),
+                _ptr(stats)), "icp_plane")
+        return pose[:9].reshape(3, 3).copy(), pose[9:].copy(), stats, hist
+
     def kd_build(self, pts, depth0=0):
         """Reference buildKDTree permutation of `pts` (returns a new array)."""
         p = np.array(pts, np.float64, order="C").reshape(-1, 3)
@@ -348,6 +458,33 @@ class NavGpu:
         self._check(self.L.navgpu_icp_dev(
             self.h, _ptr(src), nq, _ptr(tgt), nt, iters, float(max_dist), _ptr(mask),
             _ptr(pose), _ptr(hist), _ptr(stats)), "icp_dev")
+
+    def normals_dev(self, pts, n, idx, stride, k, viewpoint, normals, curv=None):
+        """viewpoint: 3 host doubles or None; the rest device pointers."""
+        vp = self._viewpoint(viewpoint)
+        self._check(self.L.navgpu_normals_dev(self.h, _ptr(pts), n, _ptr(idx), stride, k,
+                                              _ptr(vp), _ptr(normals), _ptr(curv)),
+                    "normals_dev")
+
+    def cloud_normals_dev(self, pts, n, k, viewpoint, normals, curv=None):
+        vp = self._viewpoint(viewpoint)
+        self._check(self.L.navgpu_cloud_normals_dev(self.h, _ptr(pts), n, k, _ptr(vp),
+                                                    _ptr(normals), _ptr(curv)),
+                    "cloud_normals_dev")
+
+    def align_plane_dev(self, src, nq, tgt, nt, tgt_normals, tgt_curv, idx, dist, stride,
+                        max_dist, max_curv, mask, delta, pose, stats):
+        self._check(self.L.navgpu_align_plane_dev(
+            self.h, _ptr(src), nq, _ptr(tgt), nt, _ptr(tgt_normals), _ptr(tgt_curv), _ptr(idx),
+            _ptr(dist), stride, float(max_dist), float(max_curv), _ptr(mask), _ptr(delta),
+            _ptr(pose), _ptr(stats)), "align_plane_dev")
+
+    def icp_plane_dev(self, src, nq, tgt, nt, tgt_normals, tgt_curv, iters, max_dist, max_curv,
+                      mask, pose, hist=None, stats=None):
+        self._check(self.L.navgpu_icp_plane_dev(
+            self.h, _ptr(src), nq, _ptr(tgt), nt, _ptr(tgt_normals), _ptr(tgt_curv), iters,
+            float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist), _ptr(stats)),
+            "icp_plane_dev")
 
     def kd_build_dev(self, pts, n, depth0=0):
         self._check(self.L.navgpu_kd_build_dev(self.h, _ptr(pts), n, depth0), "kd_build_dev")

@@ -1,0 +1,216 @@
+"""The solvers of the point-to-plane registration (nav-slam_amd/csrc/
+plane_solve.h) on the host: tests/plane_solve_driver.cpp is compiled against
+the header with the address and undefined-behaviour sanitizers and run as a
+stand-alone program (hex floats in on stdin, results back). The checkers are
+numpy.linalg.eigh for sym3_eig and the numpy restatement ref_plane
+(tests/plane_ref.py) for plane_solve; the reference project has neither."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from plane_ref import EPS, check_step, knn_numpy, plane_moments, ref_normals, ref_plane
+
+CSRC = os.path.join(ROOT, "nav-slam_amd", "csrc")
+DRIVER = os.path.join(ROOT, "tests", "plane_solve_driver.cpp")
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("plane_solve") / "plane_solve_driver")
+    subprocess.run(["g++", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover", f"-I{CSRC}", DRIVER, "-o", exe], check=True)
+
+    def run(cmd, *arrays):
+        vals = np.concatenate([np.asarray(a, np.float64).ravel() for a in arrays])
+        line = cmd + " " + " ".join(float(v).hex() for v in vals) + "\n"
+        r = subprocess.run([exe], input=line, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        return np.array([float.fromhex(w) for w in r.stdout.split()])
+    return run
+
+
+def rot(axis, deg):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    th = np.deg2rad(deg)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+# ------------------------------------------------------------------ sym3_eig
+def cov(x):
+    xc = x - x.mean(0)
+    return xc.T @ xc
+
+
+def _eig_cases():
+    rng = np.random.default_rng(17)
+    c = {}
+    patch = rng.uniform(-50.0, 50.0, (8, 3)) * np.array([1.0, 0.6, 0.0])
+    patch[:, 2] = rng.normal(0.0, 0.5, 8)
+    c["planar_patch"] = cov(patch @ rot((1, 2, 3), 40.0).T)
+    c["blob"] = cov(rng.normal(0.0, 10.0, (16, 3)))
+    c["diagonal"] = np.diag([7.0, 0.25, 3.0])
+    line = np.outer(np.arange(8.0), [3.0, -2.0, 5.0]) + np.array([10.0, 20.0, -30.0])
+    c["rank1"] = cov(line)
+    c["zero"] = np.zeros((3, 3))
+    c["scaled_up"] = c["planar_patch"] * 1e14
+    c["scaled_down"] = c["planar_patch"] * 1e-14
+    return c
+
+
+EIG_CASES = ["planar_patch", "blob", "diagonal", "rank1", "zero", "scaled_up", "scaled_down"]
+
+
+def eig3(driver, C):
+    out = driver("eig3", [C[0, 0], C[0, 1], C[0, 2], C[1, 1], C[1, 2], C[2, 2]])
+    assert out.shape == (12,)
+    return out[:3], out[3:].reshape(3, 3)     # vec[k] the eigenvector of lam[k]
+
+
+@pytest.mark.parametrize("name", EIG_CASES)
+def test_eig3_matches_eigh(driver, name):
+    C = _eig_cases()[name]
+    lam, vec = eig3(driver, C)
+    lr, vr = np.linalg.eigh(C)
+    l2 = lr[2]
+    print(f"{name}: lam {lam} ref {lr}")
+    assert lam[0] <= lam[1] <= lam[2]
+    assert np.abs(lam - lr).max() <= 64 * EPS * l2
+    if name == "zero":
+        assert np.array_equal(lam, np.zeros(3)) and np.array_equal(vec, np.eye(3))
+        return
+    if name == "diagonal":     # no rotation: the entries, sorted, and unit axes, exactly
+        assert np.array_equal(lam, [0.25, 3.0, 7.0])
+        assert np.array_equal(vec, [[0, 1, 0], [0, 0, 1], [1, 0, 0]])
+        return
+    # the eigenvectors are orthonormal whatever the gaps
+    assert np.abs(vec @ vec.T - np.eye(3)).max() <= 16 * EPS
+    if name == "rank1":
+        # integer collinear points: no plane, and the kernel must see that
+        assert lam[1] <= 1e-14 * lam[2] and abs(lam[0]) <= 1e-14 * lam[2]
+        d = np.array([3.0, -2.0, 5.0]) / np.sqrt(38.0)
+        assert np.abs(np.abs(vec[2] @ d) - 1.0) <= 16 * EPS
+        return
+    gap = (lr[1] - lr[0]) / l2
+    assert gap >= 1e-6
+    tol_v = 1024 * EPS / gap
+    s = 1.0 if vec[0] @ vr[:, 0] >= 0 else -1.0
+    err = np.abs(s * vec[0] - vr[:, 0]).max()
+    print(f"{name}: gap {gap:.3g} |n - nref| {err:.3g} (tol {tol_v:.3g})")
+    assert err <= tol_v
+
+
+# --------------------------------------------------------------- plane_solve
+T_TRUE = np.array([3.0, -2.0, 1.5])
+R_TRUE = rot((1, -2, 3), 0.4)
+OFFSET = np.array([1e7, -2e7, 3e6])
+
+
+def box_case(n=240, seed=9):
+    """points on a 2^-10 mm lattice in a 1 m cube (so that OFFSET adds to them
+    exactly), a small known motion, normals drawn from the three axes"""
+    rng = np.random.default_rng(seed)
+    p = np.round(rng.uniform(-500.0, 500.0, (n, 3)) * 1024.0) / 1024.0
+    q = np.round((p @ R_TRUE.T + T_TRUE) * 1024.0) / 1024.0
+    nrm = np.eye(3)[rng.integers(0, 3, n)] * rng.choice([-1.0, 1.0], n)[:, None]
+    return p, q, nrm
+
+
+_ROOM = {}
+
+
+def room_case():
+    """l9_pair(16, 256, seed=3): the pairs of the first ICP iteration at a
+    150 mm gate, normals from the target's own 8-NN, viewpoint the origin"""
+    if not _ROOM:
+        from navslam.synth import l9_pair
+        src, tgt = l9_pair(16, 256, seed=3)
+        src, tgt = src.reshape(-1, 3), tgt.reshape(-1, 3)
+        nn8, _ = knn_numpy(tgt, tgt, 8)
+        nrm, curv, valid, _ = ref_normals(tgt, nn8, 8, viewpoint=(0.0, 0.0, 0.0))
+        idx, dist = knn_numpy(tgt, src, 1)
+        idx, dist = idx[:, 0], dist[:, 0]
+        keep = (dist <= 150.0) & valid[idx]
+        _ROOM["case"] = (src[keep], tgt[idx[keep]], nrm[idx[keep]])
+    return _ROOM["case"]
+
+
+def solve(driver, m):
+    out = driver("plane", m)
+    assert out.shape == (18,)
+    return out[:9].reshape(3, 3), out[9:12], out[12:]
+
+
+@pytest.mark.parametrize("name", ["box", "room"])
+def test_plane_matches_restatement(driver, name):
+    p, q, nrm = box_case() if name == "box" else room_case()
+    ref = ref_plane(p, q, nrm)
+    assert ref["kappa"] <= 1e3, ref["kappa"]
+    if name == "room":
+        # a well-posed scene: pivots of order 1 (numpy's: 0.967 .. 1), ten
+        # orders above kPlanePivotMin
+        assert len(p) >= 3000 and ref["pivots"].min() >= 0.9, ref["pivots"]
+    m = plane_moments(p, q, nrm, bad=2.0)
+    R, t, st = solve(driver, m)
+    assert st[3] == 2.0
+    check_step(R, t, st, ref, what=name)
+    if name == "box":
+        # the step recovers the small motion to the linearisation's accuracy
+        assert np.abs(R - R_TRUE).max() <= 1e-3 and np.abs(t - T_TRUE).max() <= 0.5
+
+
+def test_plane_large_offset(driver):
+    p, q, nrm = box_case()
+    ref0 = ref_plane(p, q, nrm)
+    po, qo = p + OFFSET, q + OFFSET
+    assert np.array_equal(po - OFFSET, p) and np.array_equal(qo - OFFSET, q)   # exact
+    ref = ref_plane(po, qo, nrm)
+    assert ref["kappa"] <= 1e3
+    R, t, st = solve(driver, plane_moments(po, qo, nrm))
+    check_step(R, t, st, ref, what="offset")
+    # and the same motion as at offset 0: t' = t0 + OFFSET - R0 OFFSET
+    want_t = ref0["t"] + OFFSET - ref0["R"] @ OFFSET
+    eR, et = np.abs(R - ref0["R"]).max(), np.abs(t - want_t).max()
+    tol_R = ref["tol_R"] + ref0["tol_R"]
+    tol_t = ref["tol_t"] + ref0["tol_t"] + 2 * tol_R * np.linalg.norm(OFFSET)
+    print(f"offset vs 0: |dR| {eR:.3g} (tol {tol_R:.3g}) |dt| {et:.3g} (tol {tol_t:.3g})")
+    assert eR <= tol_R and et <= tol_t
+
+
+def refused(st, n, rms):
+    return st[0] == n and st[1] == rms and st[2] == st[1] and st[4] == 0.0
+
+
+@pytest.mark.parametrize("n", [0, 5])
+def test_plane_too_few_pairs_refused(driver, n):
+    p, q, nrm = box_case(n=n, seed=n + 1)
+    m = plane_moments(p, q, nrm, bad=3.0)
+    R, t, st = solve(driver, m)
+    assert np.array_equal(R, np.eye(3)) and np.array_equal(t, np.zeros(3))
+    rms = np.sqrt(m[32] / n) if n else 0.0
+    assert refused(st, n, rms) and st[3] == 3.0 and st[5] == 0.0
+
+
+@pytest.mark.parametrize("normal,why", [((0.0, 0.0, 1.0), "diagonal"),
+                                        ((1.0 / 3, 2.0 / 3, 2.0 / 3), "pivot")])
+def test_plane_parallel_normals_refused(driver, normal, why):
+    p, q, _ = box_case()
+    nrm = np.tile(np.asarray(normal), (len(p), 1))
+    m = plane_moments(p, q, nrm)
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = m[5:26]
+    if why == "diagonal":
+        assert A[2, 2] == 0.0 and A[3, 3] == 0.0       # omega_z and tau_x, tau_y are free
+    else:
+        assert (np.diag(A) > 0).all()
+    R, t, st = solve(driver, m)
+    assert np.array_equal(R, np.eye(3)) and np.array_equal(t, np.zeros(3))
+    assert refused(st, len(p), np.sqrt(m[32] / len(p)))
+    print(f"{why}: smallest pivot reported {st[5]:.3g}")
+    assert st[5] <= 1e-10
+    if why == "diagonal":
+        assert st[5] == 0.0
