@@ -1,10 +1,11 @@
 // align_solve.h — closed-form rigid fit (Horn's unit-quaternion method) from
 // the centred moments of a set of point pairs, and pose composition. Plain
 // C++ for host and device alike: no HIP headers, no libm beyond sqrt, only
-// + - * / sqrt in f64 and no contraction, so that the device (k_align_solve,
-// align.hip) and a host build (tests/align_solve_driver.cpp) give the same
+// + - * / sqrt in f64 and no contraction, so that the device (k_reg_solve,
+// reg_step.h) and a host build (tests/align_solve_driver.cpp) give the same
 // bits. Not part of the reference: its optimiser never fits a rotation
-// (src/slam.c:300-389).
+// (src/slam.c:300-389). step_begin, jacobi_angle and quat_to_rot are shared
+// with plane_solve.h.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -33,18 +34,51 @@ constexpr double kAlignEps = 0x1p-52;
 NV_HD inline double nv_sqrt(double v) { return __builtin_sqrt(v); }
 NV_HD inline double nv_abs(double v) { return v < 0.0 ? -v : v; }
 
+// The opening of a step's solver: stats = n, rms before (sqrt(ss / n), twice:
+// rms after = rms before until a fit replaces it), bad indices; delta = the
+// identity.
+NV_HD inline void step_begin(double n, double ss, double bad, double delta[12], double *stats) {
+  const double rms0 = n > 0.0 ? nv_sqrt(ss / n) : 0.0;
+  stats[0] = n;
+  stats[1] = rms0;
+  stats[2] = rms0;
+  stats[3] = bad;
+  for (int i = 0; i < 12; ++i) delta[i] = 0.0;
+  delta[0] = delta[4] = delta[8] = 1.0;
+}
+
+// The Jacobi rotation that annihilates apq of the symmetric pivot block
+// (app, apq; apq, aqq), apq != 0: t = tan, c = cos, s = sin of its angle.
+NV_HD inline void jacobi_angle(double app, double aqq, double apq, double &t, double &c,
+                               double &s) {
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double at = nv_abs(theta);
+  // for |theta| beyond 2^500 theta^2 + 1 would overflow: t = 1/(2 theta)
+  t = at > 0x1p500 ? 0.5 / at : 1.0 / (at + nv_sqrt(theta * theta + 1.0));
+  if (theta < 0.0) t = -t;
+  c = 1.0 / nv_sqrt(t * t + 1.0);
+  s = t * c;
+}
+
+// R (row-major) of the unit quaternion (w, x, y, z)
+NV_HD inline void quat_to_rot(double w, double x, double y, double z, double R[9]) {
+  R[0] = 1.0 - 2.0 * (y * y + z * z);
+  R[1] = 2.0 * (x * y - w * z);
+  R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z);
+  R[4] = 1.0 - 2.0 * (x * x + z * z);
+  R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y);
+  R[7] = 2.0 * (y * z + w * x);
+  R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
 // delta = R (row-major) then t, with q ~ R p + t in the least-squares sense;
 // stats = n, rms |q - p| before, rms |q - (R p + t)| after, bad indices.
 // Fewer than 3 pairs: the identity, and rms after = rms before.
 NV_HD inline void align_solve(const double m[kAlignMoments], double delta[12], double stats[4]) {
   const double n = m[0];
-  const double rms0 = n > 0.0 ? nv_sqrt(m[7] / n) : 0.0;
-  stats[0] = n;
-  stats[1] = rms0;
-  stats[2] = rms0;
-  stats[3] = m[19];
-  for (int i = 0; i < 12; ++i) delta[i] = 0.0;
-  delta[0] = delta[4] = delta[8] = 1.0;
+  step_begin(n, m[7], m[19], delta, stats);
   if (!(n >= 3.0)) return;
 
   const double Sxx = m[8], Sxy = m[9], Sxz = m[10];
@@ -82,13 +116,8 @@ NV_HD inline void align_solve(const double m[kAlignMoments], double delta[12], d
       for (int q = p + 1; q < 4; ++q) {
         const double apq = A[p][q];
         if (apq == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double at = nv_abs(theta);
-        // for |theta| beyond 2^500 theta^2 + 1 would overflow: t = 1/(2 theta)
-        double t = at > 0x1p500 ? 0.5 / at : 1.0 / (at + nv_sqrt(theta * theta + 1.0));
-        if (theta < 0.0) t = -t;
-        const double c = 1.0 / nv_sqrt(t * t + 1.0);
-        const double s = t * c;
+        double t, c, s;
+        jacobi_angle(A[p][p], A[q][q], apq, t, c, s);
         for (int k = 0; k < 4; ++k) {  // A <- A J
           const double akp = A[k][p], akq = A[k][q];
           A[k][p] = c * akp - s * akq;
@@ -117,15 +146,7 @@ NV_HD inline void align_solve(const double m[kAlignMoments], double delta[12], d
   y /= nrm;
   z /= nrm;
   double *R = delta;
-  R[0] = 1.0 - 2.0 * (y * y + z * z);
-  R[1] = 2.0 * (x * y - w * z);
-  R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z);
-  R[4] = 1.0 - 2.0 * (x * x + z * z);
-  R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y);
-  R[7] = 2.0 * (y * z + w * x);
-  R[8] = 1.0 - 2.0 * (x * x + y * y);
+  quat_to_rot(w, x, y, z, R);
   const double *pb = m + 1, *qb = m + 4;
   for (int i = 0; i < 3; ++i)
     delta[9 + i] = qb[i] - ((R[3 * i] * pb[0] + R[3 * i + 1] * pb[1]) + R[3 * i + 2] * pb[2]);

@@ -2,7 +2,8 @@
 // navgpu.hip (per-row mode, curvature, KD build, host plumbing), knn.hip
 // (global-mode grid index and exact k-NN), align.hip (rigid registration
 // on the k-NN's output) and plane.hip (surface normals and point-to-plane
-// registration on it). Internal: never installed.
+// registration on it; the two share their step, ICP loop and host staging in
+// reg_step.h). Internal: never installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -307,5 +308,10 @@ int ensure_aux(navgpu_ctx *ctx);
 int launch_curvature(const double *pts0, int32_t *mask0, double *curv0,
                      const double *pts1, int32_t *mask1, double *curv1, int R, int C,
                      hipStream_t stream);
+
+// out = t + R p for n points, the 12-double pose (R row-major, then t) read
+// from device memory; align.hip
+int transform_pose_run(navgpu_ctx *ctx, const double *pts, size_t n, const double *pose,
+                       double *out);
 
 }  // namespace nv

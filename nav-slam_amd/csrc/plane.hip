@@ -1,16 +1,16 @@
 // plane.hip — point-to-plane registration on the global k-NN's output:
-// surface normals from each point's k-neighbourhood (k_normals), the gated
-// point-to-plane moments (k_plane_moments), the linearised step
-// (k_plane_solve, plane_solve.h) and the ICP loop over them. Fourth
-// translation unit of libnavgpu.so. Beyond the reference, which has neither
-// normals nor a rotation fit; the checkers are the numpy restatements in
-// tests/test_gpu_plane.py. DESIGN.md §11.
+// surface normals from each point's k-neighbourhood (k_normals) and the
+// point-to-plane metric of the shared two-pass step (reg_step.h), whose
+// linearised solver is plane_solve.h's. Fourth translation unit of
+// libnavgpu.so. Beyond the reference, which has neither normals nor a
+// rotation fit; the checkers are the numpy restatements in tests/reg_ref.py.
+// DESIGN.md §11.
 //
-//   k_normals           mu, centred covariance, sym3_eig, orientation
-//   k_plane_moments<0>  pass A: n, sum p, bad indices
-//   k_plane_finish      pbar from the pass-A partials
-//   k_plane_moments<1>  pass B: A (21), b (6), sum r^2 about pbar
-//   k_plane_solve       plane_solve, stats, pose <- delta o pose
+//   k_normals   mu, centred covariance, sym3_eig, orientation
+//   pass A      n, sum p, bad indices
+//   finish      pbar from the pass-A partials
+//   pass B      A (21), b (6), sum r^2 about pbar
+//   solve       plane_solve, stats, pose <- delta o pose
 //
 // The sums follow align.hip's rule (det_reduce.h): reproducible bit for bit,
 // no floating-point atomics, a grid that depends on nq alone.
@@ -18,6 +18,7 @@
 
 #include "plane_solve.h"
 #include "det_reduce.h"
+#include "reg_step.h"
 
 using namespace nv;
 
@@ -157,259 +158,104 @@ int cloud_normals_run(navgpu_ctx *ctx, const double *pts, size_t n, int k, const
 }
 
 // --------------------------------------------------------------- plane step
-constexpr int kPlaneBlock = kRedBlock;
-// Independent queries in flight per lane. Pass B keeps 28 f64 accumulators
-// (56 VGPRs) per lane, and a query in flight holds p, q and the normal (18
-// VGPRs) beside its index, distance, mask and curvature: two of them stay
-// within the 128-VGPR budget of four waves per SIMD, four do not.
-constexpr int kPlaneU = 2;
-constexpr int kPlaneTile = kPlaneBlock * kPlaneU;  // queries per block and trip
-constexpr int kPlaneMaxGrid = 1024;
-constexpr int kPlaneRow = 32;  // doubles per partial row (256 B)
-constexpr int kPA = 5;         // pass A: n, sum p, bad
-constexpr int kPB = 28;        // pass B: A upper (21), b (6), sum r^2
-
 struct PlaneIn {
-  const double *src, *tgt, *nrm, *curv;  // the target's are never null here
+  const double *src, *tgt, *nrm, *curv;  // the target's are never null in a kernel (no_target)
   const int32_t *idx;
   const double *dist;
   const int32_t *mask;  // nullable
   size_t nq;
   int nt, stride;
   double max_dist, max_curv;
+  bool has_target() const { return tgt && nrm && curv; }
+  bool gates_are_numbers() const { return max_dist == max_dist && max_curv == max_curv; }
+  void no_target(const double *p) { tgt = nrm = curv = p; }
 };
 
-// One pass over the queries. k_align_moments' gate (index in range, distance
-// <= max_dist, mask set) and one more condition, the neighbour's curvature
-// <= max_curv: a NaN curvature (no normal there) fails it. A query rejected
-// by the first three has its j replaced by 0 before any gather, so an index
-// outside the cloud is counted (pass A) and never dereferenced.
-template <int PASS>
-__global__ __launch_bounds__(kPlaneBlock) void k_plane_moments(PlaneIn a,
-                                                               const double *__restrict__ cent,
-                                                               double *__restrict__ part) {
-  constexpr int NV = PASS ? kPB : kPA;
-  double acc[NV];
+// The shared gate (reg_step.h) and one more condition, the neighbour's
+// curvature <= max_curv: a NaN curvature (no normal there) fails it.
+struct PlaneMetric {
+  // Independent queries in flight per lane. Pass B keeps 28 f64 accumulators
+  // (56 VGPRs) per lane, and a query in flight holds p, q and the normal (18
+  // VGPRs) beside its index, distance, mask and curvature: two of them stay
+  // within the 128-VGPR budget of four waves per SIMD, four do not.
+  static constexpr int kU = 2;
+  static constexpr int kNA = 5;    // pass A: n, sum p, bad
+  static constexpr int kNB = 28;   // pass B: A upper (21), b (6), sum r^2
+  static constexpr int kRow = 32;  // doubles per partial row (256 B)
+  static constexpr int kCentroids = 1;  // finish record: n, pbar, bad
+  static constexpr int kStats = 6;
+  static constexpr int kPart = kPlanePart, kOut = kPlaneOut;
+  static constexpr const char *kRegion = "align_plane";
+  using In = PlaneIn;
+  struct Pair {
+    double cv, p[3], t[3], nn[3];  // t and nn in pass B only
+  };
+
+  template <int PASS>
+  static __device__ __forceinline__ void gather(const In &a, size_t q, int j, Pair &g) {
+    g.cv = a.curv[j];
 #pragma unroll
-  for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-  double pb[3] = {0.0, 0.0, 0.0};
-  if (PASS) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pb[c] = cent[1 + c];
-  }
-  const size_t ntile = (a.nq + kPlaneTile - 1) / kPlaneTile;
-  for (size_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
-    const size_t q0 = tile * kPlaneTile + threadIdx.x;
-    size_t qq[kPlaneU];
-    int j[kPlaneU], mk[kPlaneU];
-    bool ok[kPlaneU], bad[kPlaneU];
-    double d[kPlaneU], cv[kPlaneU];
-    // every load of a phase is issued before the first is consumed
-#pragma unroll
-    for (int u = 0; u < kPlaneU; ++u) {
-      const size_t q = q0 + (size_t)u * kPlaneBlock;
-      qq[u] = q < a.nq ? q : a.nq - 1;  // ntile > 0 implies nq > 0
-      j[u] = a.idx[qq[u] * a.stride];
-      d[u] = a.dist[qq[u] * a.stride];
-      mk[u] = 1;
-    }
-    if (a.mask) {
-#pragma unroll
-      for (int u = 0; u < kPlaneU; ++u) mk[u] = a.mask[qq[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < kPlaneU; ++u) {
-      const bool in = q0 + (size_t)u * kPlaneBlock < a.nq;
-      const int jj = j[u];
-      ok[u] = in & (jj >= 0) & (jj < a.nt) & (d[u] <= a.max_dist) & (mk[u] != 0);
-      bad[u] = in & ((jj < -1) | (jj >= a.nt));
-      j[u] = ok[u] ? jj : 0;
-    }
-    double p[kPlaneU][3], t[kPlaneU][3], nn[kPlaneU][3];
-#pragma unroll
-    for (int u = 0; u < kPlaneU; ++u) {
-      cv[u] = a.curv[j[u]];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        p[u][c] = a.src[3 * qq[u] + c];
-        if (PASS) {
-          t[u][c] = a.tgt[3 * (size_t)j[u] + c];
-          nn[u][c] = a.nrm[3 * (size_t)j[u] + c];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < kPlaneU; ++u) {
-      const bool take = ok[u] & (cv[u] <= a.max_curv);
-      if (PASS == 0) {
-        if (bad[u]) acc[4] += 1.0;
-        if (take) {
-          acc[0] += 1.0;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) acc[1 + c] += p[u][c];
-        }
-      } else if (take) {
-        const double x = p[u][0] - pb[0], y = p[u][1] - pb[1], z = p[u][2] - pb[2];
-        const double n0 = nn[u][0], n1 = nn[u][1], n2 = nn[u][2];
-        double J[6];
-        J[0] = y * n2 - z * n1;
-        J[1] = z * n0 - x * n2;
-        J[2] = x * n1 - y * n0;
-        J[3] = n0;
-        J[4] = n1;
-        J[5] = n2;
-        const double r = ((t[u][0] - p[u][0]) * n0 + (t[u][1] - p[u][1]) * n1) +
-                         (t[u][2] - p[u][2]) * n2;
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-          for (int k = i; k < 6; ++k) acc[e++] += J[i] * J[k];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r;
-        acc[27] += r * r;
+    for (int c = 0; c < 3; ++c) {
+      g.p[c] = a.src[3 * q + c];
+      if (PASS) {
+        g.t[c] = a.tgt[3 * (size_t)j + c];
+        g.nn[c] = a.nrm[3 * (size_t)j + c];
       }
     }
   }
-  block_sum<NV>(acc, part + (size_t)blockIdx.x * kPlaneRow);
-}
 
-// cent = n, pbar, bad indices
-__global__ __launch_bounds__(kPlaneBlock) void k_plane_finish(const double *__restrict__ partA,
-                                                              int nblk, double *__restrict__ cent) {
-  __shared__ double o[kPA];
-  combine_rows<kPA, kPlaneRow>(partA, nblk, o);
-  if (threadIdx.x == 0) {
-    const double n = o[0];
-    cent[0] = n;
-    for (int c = 0; c < 3; ++c) cent[1 + c] = n > 0.0 ? o[1 + c] / n : 0.0;
-    cent[4] = o[4];
+  static __device__ __forceinline__ bool accept(const In &a, const Pair &g) {
+    return g.cv <= a.max_curv;
   }
-}
 
-__global__ __launch_bounds__(kPlaneBlock) void k_plane_solve(const double *__restrict__ partB,
-                                                             int nblk,
-                                                             const double *__restrict__ cent,
-                                                             double *__restrict__ delta,
-                                                             double *__restrict__ stats,
-                                                             double *pose, double *hist) {
-  __shared__ double o[kPB];
-  combine_rows<kPB, kPlaneRow>(partB, nblk, o);
-  if (threadIdx.x != 0) return;
-  double m[kPlaneMoments], d[12], st[6];
-  for (int i = 0; i < 5; ++i) m[i] = cent[i];
-  for (int i = 0; i < kPB; ++i) m[5 + i] = o[i];
-  plane_solve(m, d, st);
-  for (int i = 0; i < 12; ++i) delta[i] = d[i];
-  for (int i = 0; i < 6; ++i) stats[i] = st[i];
-  if (pose) {
-    double P[12];
-    for (int i = 0; i < 12; ++i) P[i] = pose[i];
-    pose_compose(d, P);
-    for (int i = 0; i < 12; ++i) pose[i] = P[i];
-    if (hist)
-      for (int i = 0; i < 12; ++i) hist[i] = P[i];
+  static __device__ __forceinline__ void add_a(const Pair &g, double (&acc)[kNA]) {
+    acc[0] += 1.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[1 + c] += g.p[c];
   }
-}
 
-// workspace of one plane step: pass-A rows, pass-B rows, the finish record
-constexpr size_t kPlanePartDoubles = 2 * (size_t)kPlaneMaxGrid * kPlaneRow + kPlaneRow;
-
-// The plane step on device pointers; hist (nullable) also receives the
-// composed pose.
-int plane_run(navgpu_ctx *ctx, const double *src, size_t nq, const double *tgt, size_t nt,
-              const double *tgt_normals, const double *tgt_curv, const int32_t *idx,
-              const double *dist, int stride, double max_dist, double max_curv,
-              const int32_t *mask, double *delta, double *pose, double *stats, double *hist) {
-  ARG_CHECK(ctx && delta && stats);
-  ARG_CHECK(stride >= 1 && stride <= 16);
-  ARG_CHECK(max_dist == max_dist && max_curv == max_curv);  // not a NaN
-  ARG_CHECK(nq < (size_t)INT32_MAX && nt < (size_t)INT32_MAX);
-  ARG_CHECK(nq == 0 || (src && idx && dist));
-  ARG_CHECK(nt == 0 || (tgt && tgt_normals && tgt_curv));
-  double *part;
-  RC(ws(ctx, kPlanePart, kPlanePartDoubles, &part));
-  double *partA = part, *partB = part + (size_t)kPlaneMaxGrid * kPlaneRow;
-  double *cent = partB + (size_t)kPlaneMaxGrid * kPlaneRow;
-  // an empty target accepts nothing, and j = 0 then reads the workspace
-  const PlaneIn in{src, nt ? tgt : part, nt ? tgt_normals : part, nt ? tgt_curv : part, idx, dist,
-                   mask, nq, (int)nt, stride, max_dist, max_curv};
-  const unsigned grid = det_grid(nq, kPlaneTile, kPlaneMaxGrid);
-  hipStream_t s = ctx->stream;
-  TimedRegion tr(ctx, "align_plane");
-  hipLaunchKernelGGL(k_plane_moments<0>, dim3(grid), dim3(kPlaneBlock), 0, s, in,
-                     (const double *)nullptr, partA);
-  CHECK_LAUNCH("k_plane_moments<0>");
-  hipLaunchKernelGGL(k_plane_finish, dim3(1), dim3(kPlaneBlock), 0, s, (const double *)partA,
-                     (int)grid, cent);
-  CHECK_LAUNCH("k_plane_finish");
-  hipLaunchKernelGGL(k_plane_moments<1>, dim3(grid), dim3(kPlaneBlock), 0, s, in,
-                     (const double *)cent, partB);
-  CHECK_LAUNCH("k_plane_moments<1>");
-  hipLaunchKernelGGL(k_plane_solve, dim3(1), dim3(kPlaneBlock), 0, s, (const double *)partB,
-                     (int)grid, (const double *)cent, delta, stats, pose, hist);
-  CHECK_LAUNCH("k_plane_solve");
-  return NAVGPU_OK;
-}
-
-int icp_plane_run(navgpu_ctx *ctx, const double *src, size_t nq, const double *tgt, size_t nt,
-                  const double *tgt_normals, const double *tgt_curv, int iters, double max_dist,
-                  double max_curv, const int32_t *mask, double *pose, double *hist,
-                  double *stats) {
-  ARG_CHECK(ctx && pose);
-  ARG_CHECK(iters >= 1 && iters <= 64);
-  ARG_CHECK(nq < (size_t)INT32_MAX / 2 && nt < (size_t)INT32_MAX / 2);  // navgpu_knn_dev's range
-  ARG_CHECK(nq == 0 || src);
-  ARG_CHECK(nt == 0 || (tgt && tgt_normals && tgt_curv));
-  double *cur, *nnd, *scratch;
-  int32_t *nni;
-  RC(ws(ctx, kIcpCur, 3 * std::max<size_t>(nq, 1), &cur));
-  RC(ws(ctx, kIcpIdx, std::max<size_t>(nq, 1), &nni));
-  RC(ws(ctx, kIcpDist, std::max<size_t>(nq, 1), &nnd));
-  RC(ws(ctx, kPlaneOut, 18, &scratch));
-  for (int i = 0; i < iters; ++i) {
-    {
-      TimedRegion tr(ctx, "icp_transform");
-      RC(navgpu_transform_pose_dev(ctx, src, nq, pose, cur));
-    }
-    RC(navgpu_knn_dev(ctx, tgt, nt, cur, nq, 1, nni, nnd));
-    RC(plane_run(ctx, cur, nq, tgt, nt, tgt_normals, tgt_curv, nni, nnd, 1, max_dist, max_curv,
-                 mask, scratch, pose, stats ? stats + 6 * (size_t)i : scratch + 12,
-                 hist ? hist + 12 * (size_t)i : nullptr));
+  // pb = pbar
+  static __device__ __forceinline__ void add_b(const Pair &g, const double (&pb)[3],
+                                               double (&acc)[kNB]) {
+    const double x = g.p[0] - pb[0], y = g.p[1] - pb[1], z = g.p[2] - pb[2];
+    const double n0 = g.nn[0], n1 = g.nn[1], n2 = g.nn[2];
+    double J[6];
+    J[0] = y * n2 - z * n1;
+    J[1] = z * n0 - x * n2;
+    J[2] = x * n1 - y * n0;
+    J[3] = n0;
+    J[4] = n1;
+    J[5] = n2;
+    const double r = ((g.t[0] - g.p[0]) * n0 + (g.t[1] - g.p[1]) * n1) + (g.t[2] - g.p[2]) * n2;
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int k = i; k < 6; ++k) acc[e++] += J[i] * J[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r;
+    acc[27] += r * r;
   }
-  return NAVGPU_OK;
-}
 
-// host arrays onto the context's stream; a null or empty source gives null
-template <class T>
-int to_dev(navgpu_ctx *ctx, int slot, const T *host, size_t count, T **dev) {
-  *dev = nullptr;
-  if (!host || !count) return NAVGPU_OK;
-  RC(ws(ctx, slot, count, dev));
-  HIP_TRY(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  return NAVGPU_OK;
-}
+  static __device__ void solve(const double *cent, const double *o, double d[12],
+                               double st[kStats]) {
+    double m[kPlaneMoments];
+    for (int i = 0; i < 5; ++i) m[i] = cent[i];
+    for (int i = 0; i < kNB; ++i) m[5 + i] = o[i];
+    plane_solve(m, d, st);
+  }
 
-// the ICP loop on uploaded clouds, its results back on the host
-int icp_plane_finish_host(navgpu_ctx *ctx, const double *ds, size_t nq, const double *dt,
-                          size_t nt, const double *dn, const double *dc, int iters,
-                          double max_dist, double max_curv, const int32_t *dm, double pose[12],
-                          double *hist, double *stats) {
-  hipStream_t s = ctx->stream;
-  double *dout;  // pose[12], hist[iters][12], stats[iters][6]
-  RC(ws(ctx, kH5, 12 + 18 * (size_t)iters, &dout));
-  double *dhist = dout + 12, *dstats = dhist + 12 * (size_t)iters;
-  HIP_TRY(hipMemcpyAsync(dout, pose, 12 * sizeof(double), hipMemcpyHostToDevice, s));
-  RC(icp_plane_run(ctx, ds, nq, dt, nt, dn, dc, iters, max_dist, max_curv, dm, dout, dhist,
-                   dstats));
-  HIP_TRY(hipMemcpyAsync(pose, dout, 12 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (hist)
-    HIP_TRY(hipMemcpyAsync(hist, dhist, 12 * sizeof(double) * iters, hipMemcpyDeviceToHost, s));
-  if (stats)
-    HIP_TRY(hipMemcpyAsync(stats, dstats, 6 * sizeof(double) * iters, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return nq ? navgpu_knn_check(ctx) : NAVGPU_OK;
-}
+  static int upload_target(navgpu_ctx *ctx, In &in, size_t nt) {
+    double *dt, *dn, *dc;
+    RC(to_dev(ctx, kH1, in.tgt, 3 * nt, &dt));
+    RC(to_dev(ctx, kPlaneNrm, in.nrm, 3 * nt, &dn));
+    RC(to_dev(ctx, kPlaneCurv, in.curv, nt, &dc));
+    in.tgt = dt;
+    in.nrm = dn;
+    in.curv = dc;
+    return NAVGPU_OK;
+  }
+};
 
 }  // namespace
 
@@ -468,8 +314,9 @@ int navgpu_align_plane_dev(navgpu_ctx *ctx, const double *src, size_t nq, const 
                            const int32_t *idx, const double *dist, int stride, double max_dist,
                            double max_curv, const int32_t *mask, double *delta, double *pose,
                            double *stats) {
-  return plane_run(ctx, src, nq, tgt, nt, tgt_normals, tgt_curv, idx, dist, stride, max_dist,
-                   max_curv, mask, delta, pose, stats, nullptr);
+  return step_run<PlaneMetric>(ctx, {src, tgt, tgt_normals, tgt_curv, idx, dist, mask, nq,
+                                     (int)nt, stride, max_dist, max_curv},
+                               nt, delta, pose, stats, nullptr);
 }
 
 int navgpu_align_plane_host(navgpu_ctx *ctx, const double *src, size_t nq, const double *tgt,
@@ -477,37 +324,18 @@ int navgpu_align_plane_host(navgpu_ctx *ctx, const double *src, size_t nq, const
                             const int32_t *idx, const double *dist, int stride, double max_dist,
                             double max_curv, const int32_t *mask, double Rm[9], double t[3],
                             double stats[6]) {
-  ARG_CHECK(ctx && Rm && t && stats);
-  ARG_CHECK(stride >= 1 && stride <= 16);
-  ARG_CHECK(nq == 0 || (src && idx && dist));
-  ARG_CHECK(nt == 0 || (tgt && tgt_normals && tgt_curv));
-  double *ds, *dt, *dn, *dc, *dd, *dout;
-  int32_t *di, *dm;
-  RC(to_dev(ctx, kH0, src, 3 * nq, &ds));
-  RC(to_dev(ctx, kH2, idx, nq * stride, &di));
-  RC(to_dev(ctx, kH3, dist, nq * stride, &dd));
-  RC(to_dev(ctx, kH4, mask, nq, &dm));
-  RC(to_dev(ctx, kH1, tgt, 3 * nt, &dt));
-  RC(to_dev(ctx, kPlaneNrm, tgt_normals, 3 * nt, &dn));
-  RC(to_dev(ctx, kPlaneCurv, tgt_curv, nt, &dc));
-  RC(ws(ctx, kH5, 18, &dout));
-  RC(plane_run(ctx, ds, nq, dt, nt, dn, dc, di, dd, stride, max_dist, max_curv, dm, dout,
-               nullptr, dout + 12, nullptr));
-  double out[18];
-  HIP_TRY(hipMemcpyAsync(out, dout, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  memcpy(Rm, out, 9 * sizeof(double));
-  memcpy(t, out + 9, 3 * sizeof(double));
-  memcpy(stats, out + 12, 6 * sizeof(double));
-  return NAVGPU_OK;
+  return step_host<PlaneMetric>(ctx, {src, tgt, tgt_normals, tgt_curv, idx, dist, mask, nq,
+                                      (int)nt, stride, max_dist, max_curv},
+                                nt, Rm, t, stats);
 }
 
 int navgpu_icp_plane_dev(navgpu_ctx *ctx, const double *src, size_t nq, const double *tgt,
                          size_t nt, const double *tgt_normals, const double *tgt_curv, int iters,
                          double max_dist, double max_curv, const int32_t *mask, double *pose,
                          double *hist, double *stats) {
-  return icp_plane_run(ctx, src, nq, tgt, nt, tgt_normals, tgt_curv, iters, max_dist, max_curv,
-                       mask, pose, hist, stats);
+  return icp_run<PlaneMetric>(ctx, {src, tgt, tgt_normals, tgt_curv, nullptr, nullptr, mask, nq,
+                                    (int)nt, 1, max_dist, max_curv},
+                              nt, iters, pose, hist, stats);
 }
 
 int navgpu_icp_plane_host(navgpu_ctx *ctx, const double *src, size_t nq, const double *tgt,
@@ -519,18 +347,19 @@ int navgpu_icp_plane_host(navgpu_ctx *ctx, const double *src, size_t nq, const d
   ARG_CHECK(kn >= 3 && kn <= 16);
   ARG_CHECK(nq == 0 || src);
   ARG_CHECK(nt == 0 || tgt);
-  double *ds, *dt, *dn = nullptr, *dc = nullptr;
-  int32_t *dm;
-  RC(to_dev(ctx, kH0, src, 3 * nq, &ds));
-  RC(to_dev(ctx, kH4, mask, nq, &dm));
-  RC(to_dev(ctx, kH1, tgt, 3 * nt, &dt));
+  PlaneIn in{src, tgt, nullptr, nullptr, nullptr, nullptr, mask, nq, (int)nt, 1, max_dist,
+             max_curv};
+  RC(upload_queries(ctx, in));
+  RC(PlaneMetric::upload_target(ctx, in, nt));  // the cloud alone: its normals are made here
   if (nt) {
+    double *dn, *dc;
     RC(ws(ctx, kPlaneNrm, 3 * nt, &dn));
     RC(ws(ctx, kPlaneCurv, nt, &dc));
-    RC(cloud_normals_run(ctx, dt, nt, kn, viewpoint, dn, dc));
+    RC(cloud_normals_run(ctx, in.tgt, nt, kn, viewpoint, dn, dc));
+    in.nrm = dn;
+    in.curv = dc;
   }
-  return icp_plane_finish_host(ctx, ds, nq, dt, nt, dn, dc, iters, max_dist, max_curv, dm, pose,
-                               hist, stats);
+  return icp_finish_host<PlaneMetric>(ctx, in, nt, iters, pose, hist, stats);
 }
 
 int navgpu_icp_plane_normals_host(navgpu_ctx *ctx, const double *src, size_t nq,
@@ -542,15 +371,11 @@ int navgpu_icp_plane_normals_host(navgpu_ctx *ctx, const double *src, size_t nq,
   ARG_CHECK(iters >= 1 && iters <= 64);
   ARG_CHECK(nq == 0 || src);
   ARG_CHECK(nt == 0 || (tgt && tgt_normals && tgt_curv));
-  double *ds, *dt, *dn, *dc;
-  int32_t *dm;
-  RC(to_dev(ctx, kH0, src, 3 * nq, &ds));
-  RC(to_dev(ctx, kH4, mask, nq, &dm));
-  RC(to_dev(ctx, kH1, tgt, 3 * nt, &dt));
-  RC(to_dev(ctx, kPlaneNrm, tgt_normals, 3 * nt, &dn));
-  RC(to_dev(ctx, kPlaneCurv, tgt_curv, nt, &dc));
-  return icp_plane_finish_host(ctx, ds, nq, dt, nt, dn, dc, iters, max_dist, max_curv, dm, pose,
-                               hist, stats);
+  PlaneIn in{src, tgt, tgt_normals, tgt_curv, nullptr, nullptr, mask, nq, (int)nt, 1, max_dist,
+             max_curv};
+  RC(upload_queries(ctx, in));
+  RC(PlaneMetric::upload_target(ctx, in, nt));
+  return icp_finish_host<PlaneMetric>(ctx, in, nt, iters, pose, hist, stats);
 }
 
 }  // extern "C"

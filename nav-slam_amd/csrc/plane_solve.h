@@ -3,9 +3,10 @@
 // from a neighbourhood's covariance) and the linearised point-to-plane step
 // (plane_solve). Plain C++ for host and device alike, in the manner of
 // align_solve.h: no HIP headers, only + - * / sqrt in f64, no contraction and
-// nothing but fixed-size local storage, so that the device (k_normals,
-// k_plane_solve in plane.hip) and a host build (tests/plane_solve_driver.cpp)
-// give the same bits. Not part of the reference. DESIGN.md §11.
+// nothing but fixed-size local storage, so that the device (k_normals in
+// plane.hip, k_reg_solve in reg_step.h) and a host build
+// (tests/plane_solve_driver.cpp) give the same bits. Not part of the
+// reference. DESIGN.md §11.
 #pragma once
 
 #include "align_solve.h"
@@ -33,13 +34,8 @@ NV_HD inline void eig3_rotate(double &app, double &aqq, double &apq, double &arp
                               double &v0p, double &v0q, double &v1p, double &v1q, double &v2p,
                               double &v2q) {
   if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double at = nv_abs(theta);
-  // for |theta| beyond 2^500 theta^2 + 1 would overflow: t = 1/(2 theta)
-  double t = at > 0x1p500 ? 0.5 / at : 1.0 / (at + nv_sqrt(theta * theta + 1.0));
-  if (theta < 0.0) t = -t;
-  const double c = 1.0 / nv_sqrt(t * t + 1.0);
-  const double s = t * c;
+  double t, c, s;
+  jacobi_angle(app, aqq, apq, t, c, s);
   app = app - t * apq;
   aqq = aqq + t * apq;
   apq = 0.0;
@@ -124,15 +120,9 @@ constexpr int kPlaneMoments = 33;
 // fewer than 6 pairs, a diagonal entry of A <= 0 or a pivot <= kPlanePivotMin.
 NV_HD inline void plane_solve(const double m[kPlaneMoments], double delta[12], double stats[6]) {
   const double n = m[0];
-  const double rms0 = n > 0.0 ? nv_sqrt(m[32] / n) : 0.0;
-  stats[0] = n;
-  stats[1] = rms0;
-  stats[2] = rms0;
-  stats[3] = m[4];
+  step_begin(n, m[32], m[4], delta, stats);
   stats[4] = 0.0;
   stats[5] = 0.0;
-  for (int i = 0; i < 12; ++i) delta[i] = 0.0;
-  delta[0] = delta[4] = delta[8] = 1.0;
   if (!(n >= 6.0)) return;
 
   double S[6][6], sc[6], bs[6];
@@ -188,15 +178,7 @@ NV_HD inline void plane_solve(const double m[kPlaneMoments], double delta[12], d
   qy /= nrm;
   qz /= nrm;
   double *R = delta;
-  R[0] = 1.0 - 2.0 * (qy * qy + qz * qz);
-  R[1] = 2.0 * (qx * qy - w * qz);
-  R[2] = 2.0 * (qx * qz + w * qy);
-  R[3] = 2.0 * (qx * qy + w * qz);
-  R[4] = 1.0 - 2.0 * (qx * qx + qz * qz);
-  R[5] = 2.0 * (qy * qz - w * qx);
-  R[6] = 2.0 * (qx * qz - w * qy);
-  R[7] = 2.0 * (qy * qz + w * qx);
-  R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+  quat_to_rot(w, qx, qy, qz, R);
   const double *pb = m + 1;
   for (int i = 0; i < 3; ++i)
     delta[9 + i] = x[3 + i] + (pb[i] - ((R[3 * i] * pb[0] + R[3 * i + 1] * pb[1]) + R[3 * i + 2] * pb[2]));

@@ -285,25 +285,58 @@ class NavGpu:
                                            _ptr(idx), _ptr(dist)), "knn")
         return idx, dist
 
-    def align(self, src, tgt, idx, dist, max_dist=np.inf, mask=None):
-        """One 6-DOF align step on the pairs (src[q], tgt[idx[q, 0]]) that pass
-        the gate (navgpu.h): (R[3,3], t[3], stats[4]) with tgt ~ t + R src."""
-        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
-        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
-        nq = len(src)
-        # rows of k slots per query as knn() returns them (an empty call has none)
+    # marshalling shared by align, icp, align_plane and icp_plane
+    @staticmethod
+    def _cloud(pts):
+        return np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+
+    @staticmethod
+    def _mask(mask, n, what):
+        if mask is None:
+            return None
+        mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
+        if len(mask) != n:
+            raise ValueError(what)
+        return mask
+
+    @staticmethod
+    def _rows(idx, dist, nq, what):
+        """rows of k slots per query as knn() returns them (an empty call has none)"""
         idx = np.ascontiguousarray(idx, np.int32).reshape((nq, -1) if nq else (0, 1))
         dist = np.ascontiguousarray(dist, np.float64).reshape((nq, -1) if nq else (0, 1))
         if idx.shape != dist.shape:
-            raise ValueError("align: idx and dist differ in shape")
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
-            if len(mask) != nq:
-                raise ValueError("align: one mask entry per query")
-        stride = idx.shape[1]
+            raise ValueError(f"{what}: idx and dist differ in shape")
+        return idx, dist
+
+    @staticmethod
+    def _target_normals(tgt, tgt_normals, tgt_curv, what):
+        tn = np.ascontiguousarray(tgt_normals, np.float64).reshape(-1, 3)
+        tc = np.ascontiguousarray(tgt_curv, np.float64).reshape(-1)
+        if len(tn) != len(tgt) or len(tc) != len(tgt):
+            raise ValueError(f"{what}: one normal and one curvature per target point")
+        return tn, tc
+
+    @staticmethod
+    def _pose(init):
+        """the 12 doubles (R row-major, then t) of init = (R, t); None: the identity"""
+        pose = np.zeros(12)
+        if init is None:
+            pose[[0, 4, 8]] = 1.0
+        else:
+            pose[:9] = np.asarray(init[0], np.float64).reshape(9)
+            pose[9:] = np.asarray(init[1], np.float64).reshape(3)
+        return pose
+
+    def align(self, src, tgt, idx, dist, max_dist=np.inf, mask=None):
+        """One 6-DOF align step on the pairs (src[q], tgt[idx[q, 0]]) that pass
+        the gate (navgpu.h): (R[3,3], t[3], stats[4]) with tgt ~ t + R src."""
+        src, tgt = self._cloud(src), self._cloud(tgt)
+        nq = len(src)
+        idx, dist = self._rows(idx, dist, nq, "align")
+        mask = self._mask(mask, nq, "align: one mask entry per query")
         R, t, stats = np.zeros((3, 3)), np.zeros(3), np.zeros(4)
         self._check(self.L.navgpu_align_host(
-            self.h, _ptr(src), nq, _ptr(tgt), len(tgt), _ptr(idx), _ptr(dist), stride,
+            self.h, _ptr(src), nq, _ptr(tgt), len(tgt), _ptr(idx), _ptr(dist), idx.shape[1],
             float(max_dist), _ptr(mask), _ptr(R), _ptr(t), _ptr(stats)), "align")
         return R, t, stats
 
@@ -311,18 +344,9 @@ class NavGpu:
         """Point-to-point ICP of src onto tgt, a fixed `iters` iterations from
         the pose init = (R, t) (default: the identity):
         (R[3,3], t[3], stats[iters,4], hist[iters,12])."""
-        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
-        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
-            if len(mask) != len(src):
-                raise ValueError("icp: one mask entry per source point")
-        pose = np.zeros(12)
-        if init is None:
-            pose[[0, 4, 8]] = 1.0
-        else:
-            pose[:9] = np.asarray(init[0], np.float64).reshape(9)
-            pose[9:] = np.asarray(init[1], np.float64).reshape(3)
+        src, tgt = self._cloud(src), self._cloud(tgt)
+        mask = self._mask(mask, len(src), "icp: one mask entry per source point")
+        pose = self._pose(init)
         hist = np.zeros((iters, 12))
         stats = np.zeros((iters, 4))
         self._check(self.L.navgpu_icp_host(
@@ -361,21 +385,11 @@ class NavGpu:
                     max_curv=np.inf, mask=None):
         """One point-to-plane step on the pairs (src[q], tgt[idx[q, 0]]) that
         pass the gate (navgpu.h): (R[3,3], t[3], stats[6])."""
-        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
-        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
-        tn = np.ascontiguousarray(tgt_normals, np.float64).reshape(-1, 3)
-        tc = np.ascontiguousarray(tgt_curv, np.float64).reshape(-1)
-        if len(tn) != len(tgt) or len(tc) != len(tgt):
-            raise ValueError("align_plane: one normal and one curvature per target point")
+        src, tgt = self._cloud(src), self._cloud(tgt)
+        tn, tc = self._target_normals(tgt, tgt_normals, tgt_curv, "align_plane")
         nq = len(src)
-        idx = np.ascontiguousarray(idx, np.int32).reshape((nq, -1) if nq else (0, 1))
-        dist = np.ascontiguousarray(dist, np.float64).reshape((nq, -1) if nq else (0, 1))
-        if idx.shape != dist.shape:
-            raise ValueError("align_plane: idx and dist differ in shape")
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
-            if len(mask) != nq:
-                raise ValueError("align_plane: one mask entry per query")
+        idx, dist = self._rows(idx, dist, nq, "align_plane")
+        mask = self._mask(mask, nq, "align_plane: one mask entry per query")
         R, t, stats = np.zeros((3, 3)), np.zeros(3), np.zeros(6)
         self._check(self.L.navgpu_align_plane_host(
             self.h, _ptr(src), nq, _ptr(tgt), len(tgt), _ptr(tn), _ptr(tc), _ptr(idx),
@@ -390,20 +404,11 @@ class NavGpu:
         and curvatures are the given ones, or computed once from its kn-NN and
         `viewpoint` as normals() does:
         (R[3,3], t[3], stats[iters,6], hist[iters,12])."""
-        src = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
-        tgt = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
-        if mask is not None:
-            mask = np.ascontiguousarray(mask, np.int32).reshape(-1)
-            if len(mask) != len(src):
-                raise ValueError("icp_plane: one mask entry per source point")
+        src, tgt = self._cloud(src), self._cloud(tgt)
+        mask = self._mask(mask, len(src), "icp_plane: one mask entry per source point")
         if (tgt_normals is None) != (tgt_curv is None):
             raise ValueError("icp_plane: give both tgt_normals and tgt_curv, or neither")
-        pose = np.zeros(12)
-        if init is None:
-            pose[[0, 4, 8]] = 1.0
-        else:
-            pose[:9] = np.asarray(init[0], np.float64).reshape(9)
-            pose[9:] = np.asarray(init[1], np.float64).reshape(3)
+        pose = self._pose(init)
         hist = np.zeros((iters, 12))
         stats = np.zeros((iters, 6))
         if tgt_normals is None:
@@ -413,10 +418,7 @@ class NavGpu:
                 float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist),
                 _ptr(stats)), "icp_plane")
         else:
-            tn = np.ascontiguousarray(tgt_normals, np.float64).reshape(-1, 3)
-            tc = np.ascontiguousarray(tgt_curv, np.float64).reshape(-1)
-            if len(tn) != len(tgt) or len(tc) != len(tgt):
-                raise ValueError("icp_plane: one normal and one curvature per target point")
+            tn, tc = self._target_normals(tgt, tgt_normals, tgt_curv, "icp_plane")
             self._check(self.L.navgpu_icp_plane_normals_host(
                 self.h, _ptr(src), len(src), _ptr(tgt), len(tgt), _ptr(tn), _ptr(tc), iters,
                 float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist),

@@ -1,19 +1,23 @@
-"""Timing of the surface normals, the point-to-plane step and its ICP loop
-(DESIGN.md §11). GPU only.
+"""Timing of the registration: surface normals, the point-to-point and
+point-to-plane steps and their ICP loops. GPU only.
 
 Workloads: uniform_pair() at 1,048,576 points a side and l9_pair() at
-128 x 2048. Protocol of scripts/align_bench.py: medians over the timed calls
-after warm-up, HIP events from the timing hook. Per workload it reports
+128 x 2048. Medians over the timed calls after warm-up, HIP events from the
+timing hook. Per workload it reports
   * the "normals" region (k_normals on the target's own 8-NN rows), its bytes
     model (per point: 32 B idx + 192 B gathers + 24 B self + 32 B out) and
     that rate as a fraction of the navgpu_stream_copy_dev ceiling of the run;
   * the "align_plane" region on k = 1 rows (per query, pass B: 24 B src + 4 B
     idx + 8 B dist + 24 B target + 24 B normal + 8 B curvature = 92 B; pass A
-    reads the src, idx, dist and curvature: 44 B) beside the point-to-point
-    "align" region (60 B per query and pass, two passes) of the same run;
+    reads the src, idx, dist and curvature: 44 B);
+  * the point-to-point "align" region (pass A, finish, pass B, solve; per
+    query and pass: 24 B src + 4 B idx + 8 B dist + a 24-B gather) on k = 1
+    rows and on k = 8 rows, of which the step reads slot 0;
   * a 10-iteration icp_plane_dev against a 10-iteration icp_dev, split into
-    regions, and their wall times.
-Writes the JSON to --out (default profiles/plane/bench_plane.json) and prints
+    regions (k-NN build and query, transform, step), and their wall times.
+The keys of the former align_bench.py output (profiles/align/) are those of
+the uniform_1M workload; those of plane_bench.py (profiles/plane/) are kept.
+Writes the JSON to --out (default profiles/registration/bench.json) and prints
 it on one line."""
 import argparse
 import json
@@ -34,6 +38,7 @@ PLANE_BYTES_PASS_A = 24 + 4 + 8 + 8
 PLANE_BYTES_PASS_B = 24 + 4 + 8 + 24 + 24 + 8
 PLANE_BYTES_PER_QUERY = PLANE_BYTES_PASS_A + PLANE_BYTES_PASS_B
 ALIGN_BYTES_PER_QUERY_PASS = 24 + 4 + 8 + 24
+ALIGN_PASSES = 2
 
 
 def med(v):
@@ -93,11 +98,19 @@ def workload(g, torch, dev, s, t, a, copy_gbs):
     res["align_plane_k1"].update(pairs=int(o[12]), rms_before=float(o[13]),
                                  rms_after=float(o[14]), solved=int(o[16]),
                                  min_pivot=float(o[17]))
-    ts2 = timed(g, "align", a.calls, a.warmup,
-                lambda: g.align_dev(src, n, tgt, n, idx1, dist1, 1, np.inf, None, out18, None,
-                                    out18[12:]))
-    res["align_k1"] = region_stats(ts2, 2 * ALIGN_BYTES_PER_QUERY_PASS * n, copy_gbs)
-    res["plane_over_align"] = round(float(np.median(ts) / np.median(ts2)), 4)
+    g.knn_dev(tgt, n, src, n, KN, idx8, dist8)  # the rows of the k = 8-stride align
+    g.sync()
+    for k, idx, dist in ((1, idx1, dist1), (KN, idx8, dist8)):
+        ts2 = timed(g, "align", a.calls, a.warmup,
+                    lambda: g.align_dev(src, n, tgt, n, idx, dist, k, np.inf, None, out18, None,
+                                        out18[12:]))
+        o = out18.cpu().numpy()
+        res[f"align_k{k}"] = region_stats(ts2, ALIGN_PASSES * ALIGN_BYTES_PER_QUERY_PASS * n,
+                                          copy_gbs)
+        res[f"align_k{k}"].update(pairs=int(o[12]), rms_before=float(o[13]),
+                                  rms_after=float(o[14]))
+    res["plane_over_align"] = round(res["align_plane_k1"]["ms_med"] /
+                                    res["align_k1"]["ms_med"], 4)
 
     # 10 iterations of each ICP, every region timed
     g.timing_select(None)
@@ -132,6 +145,10 @@ def workload(g, torch, dev, s, t, a, copy_gbs):
         res[kind] = {"iters": iters, "runs": a.icp_runs, "wall_ms_med": med(wall),
                      "regions_ms_med": {r: med(per[r]) for r in regions},
                      "rms_first": float(st[1]), "rms_last": float(st[width * (iters - 1) + 1])}
+        if step == "align":
+            res[kind]["align_over_knn"] = round(
+                float(np.median(per["align"]) / (np.median(per["knn_build"]) +
+                                                 np.median(per["knn_query"]))), 4)
     res["icp_plane_over_icp_wall"] = round(res["icp_plane10"]["wall_ms_med"] /
                                            res["icp10"]["wall_ms_med"], 4)
     return res
@@ -139,7 +156,8 @@ def workload(g, torch, dev, s, t, a, copy_gbs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plane", "bench_plane.json"))
+    ap.add_argument("--out",
+                    default=os.path.join(ROOT, "profiles", "registration", "bench.json"))
     ap.add_argument("--calls", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--icp-runs", type=int, default=10)
@@ -151,7 +169,8 @@ def main():
            "bytes_model_normals_per_point": NORMALS_BYTES_PER_POINT,
            "bytes_model_plane_per_query": PLANE_BYTES_PER_QUERY,
            "bytes_model_plane_pass_b": PLANE_BYTES_PASS_B,
-           "bytes_model_align_per_query_pass": ALIGN_BYTES_PER_QUERY_PASS}
+           "bytes_model_align_per_query_pass": ALIGN_BYTES_PER_QUERY_PASS,
+           "bytes_model_per_query_pass": ALIGN_BYTES_PER_QUERY_PASS, "passes": ALIGN_PASSES}
 
     # the measured HBM ceiling: a streaming device-to-device copy
     nb = 256 << 20

@@ -1,13 +1,75 @@
-"""numpy restatements of the point-to-plane registration,
-shared by tests/test_plane_solve.py (CPU) and tests/test_gpu_plane.py: the
-normals of a cloud from given neighbour rows, the centred 6 x 6 step and its
-tolerances. The reference project has none of this, so these are the checkers.
+"""numpy restatements of the registration, shared by
+tests/test_align_solve.py and tests/test_plane_solve.py (CPU) and
+tests/test_gpu_align.py, tests/test_gpu_plane.py and tests/test_gpu_icp_host.py:
+the rigid fit by SVD, the normals of a cloud from given neighbour rows, the
+centred 6 x 6 step and its tolerances, and the inputs the tests share. The
+reference project has none of this, so these are the checkers.
 """
 import numpy as np
 
 EPS = np.finfo(np.float64).eps
 LINE_TOL = 1e-12   # kPlaneLineTol
 PIVOT_MIN = 1e-10  # kPlanePivotMin
+
+
+def rot(axis, deg):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    th = np.deg2rad(deg)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def ref_align(p, q):
+    """Least-squares R, t with q ~ R p + t: f64 centroids, centred H, Kabsch
+    by SVD with the determinant fix. Also the singular values s of H, the sign
+    d and the 20 centred moments align_solve takes (align_solve.h):
+    m[17] + m[18] is Spp + Sqq."""
+    p = np.asarray(p, np.float64).reshape(-1, 3)
+    q = np.asarray(q, np.float64).reshape(-1, 3)
+    n = len(p)
+    pb = p.mean(0) if n else np.zeros(3)
+    qb = q.mean(0) if n else np.zeros(3)
+    pc, qc = p - pb, q - qb
+    H = pc.T @ qc
+    U, s, Vt = np.linalg.svd(H)
+    d = 1.0 if np.linalg.det(Vt.T @ U.T) >= 0 else -1.0
+    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
+    t = qb - R @ pb
+    m = np.concatenate([[n], pb, qb, [((q - p) ** 2).sum()], H.ravel(),
+                        [(pc ** 2).sum(), (qc ** 2).sum()], [0.0]])
+    return R, t, s, d, m
+
+
+def apply_pose(pose, pts):
+    """k_transform's operation order: t + ((R0 x + R1 y) + R2 z)"""
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    out = np.empty_like(pts)
+    for i in range(3):
+        out[:, i] = pose[9 + i] + ((pose[3 * i] * x + pose[3 * i + 1] * y) + pose[3 * i + 2] * z)
+    return out
+
+
+def strided(idx, dist, stride):
+    """rows of `stride` slots whose slot 0 is idx / dist and whose other slots
+    would break the fit if they were read"""
+    I = np.full((len(idx), stride), -5, np.int32)
+    D = np.full((len(idx), stride), np.nan)
+    I[:, 0] = idx
+    D[:, 0] = dist
+    return I, D
+
+
+_L9 = {}
+
+
+def l9_clouds():
+    """l9_pair(16, 256, seed=3) as two clouds of 4,096 points, made once"""
+    if not _L9:
+        from navslam.synth import l9_pair
+        src, tgt = l9_pair(16, 256, seed=3)
+        _L9["pair"] = (src.reshape(-1, 3), tgt.reshape(-1, 3))
+    return _L9["pair"]
 
 
 def ref_normals(pts, idx, k, viewpoint=None):

@@ -2,8 +2,8 @@
 align_solve.h) on the host: tests/align_solve_driver.cpp is compiled against
 the header with the address and undefined-behaviour sanitizers and run as a
 stand-alone program (moments in on stdin, poses back). The checker is the
-numpy restatement ref_align (Kabsch by SVD); the reference project has no
-rotation fit to compare with."""
+numpy restatement ref_align (tests/reg_ref.py, Kabsch by SVD); the reference
+project has no rotation fit to compare with."""
 import os
 import subprocess
 
@@ -11,44 +11,16 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from reg_ref import EPS, ref_align, rot
 
-EPS = np.finfo(np.float64).eps
 CSRC = os.path.join(ROOT, "nav-slam_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "align_solve_driver.cpp")
-
-
-def ref_align(p, q):
-    """Least-squares R, t with q ~ R p + t: f64 centroids, centred H, Kabsch
-    by SVD with the determinant fix. Also the singular values s, the sign d
-    and the centred moments the solver takes."""
-    p = np.asarray(p, np.float64).reshape(-1, 3)
-    q = np.asarray(q, np.float64).reshape(-1, 3)
-    n = len(p)
-    pb = p.mean(0) if n else np.zeros(3)
-    qb = q.mean(0) if n else np.zeros(3)
-    pc, qc = p - pb, q - qb
-    H = pc.T @ qc
-    U, s, Vt = np.linalg.svd(H)
-    d = 1.0 if np.linalg.det(Vt.T @ U.T) >= 0 else -1.0
-    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
-    t = qb - R @ pb
-    m = np.concatenate([[n], pb, qb, [((q - p) ** 2).sum()], H.ravel(),
-                        [(pc ** 2).sum(), (qc ** 2).sum()], [0.0]])
-    return R, t, s, d, m
 
 
 def tolerances(s, d, coord_max):
     kappa = s[0] / (s[1] + d * s[2])
     tol_R = 1024 * EPS * kappa
     return kappa, tol_R, (2 * tol_R + 64 * EPS) * coord_max
-
-
-def rot(axis, deg):
-    a = np.asarray(axis, np.float64)
-    a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(deg)
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """The 6-DOF align step and the ICP loop on the GPU (align.hip) against the
-numpy restatement ref_align (f64 centroids, centred H, Kabsch by SVD). The
+numpy restatement ref_align of tests/reg_ref.py (Kabsch by SVD). The
 reference project fits no rotation, so the restatement is the checker.
 
 Tolerances come from the data: tol_R = 1024 eps kappa with kappa = s0 /
@@ -11,11 +11,11 @@ rms before the step is one sum of n non-negative terms: 1024 eps relative.
 import numpy as np
 import pytest
 
+from reg_ref import EPS, apply_pose, l9_clouds, ref_align, rot, strided
+
 pytestmark = pytest.mark.gpu
 
-EPS = np.finfo(np.float64).eps
-
-# k_align_moments: at most 1024 blocks of 256 threads, each thread taking 4
+# the moments kernel: at most 1024 blocks of 256 threads, each thread taking 4
 # queries per trip of the grid-stride loop, so one trip of the whole launch
 # covers 1024 * 256 * 4 queries; one more makes a second trip
 ONE_TRIP = 1024 * 256 * 4
@@ -29,29 +29,6 @@ def gpu():
     g.close()
 
 
-def ref_align(p, q):
-    """Least-squares R, t with q ~ R p + t, the singular values s of the
-    centred H, the sign d of the determinant fix, and Spp + Sqq."""
-    p = np.asarray(p, np.float64).reshape(-1, 3)
-    q = np.asarray(q, np.float64).reshape(-1, 3)
-    pb, qb = p.mean(0), q.mean(0)
-    pc, qc = p - pb, q - qb
-    H = pc.T @ qc
-    U, s, Vt = np.linalg.svd(H)
-    d = 1.0 if np.linalg.det(Vt.T @ U.T) >= 0 else -1.0
-    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
-    t = qb - R @ pb
-    return R, t, s, d, (pc ** 2).sum() + (qc ** 2).sum()
-
-
-def rot(axis, deg):
-    a = np.asarray(axis, np.float64)
-    a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(deg)
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
-
-
 R0 = rot((1, 2, 3), 25.0)
 T0 = np.array([120.0, -40.0, 5.0])
 
@@ -61,7 +38,8 @@ def check_fit(R, t, stats, p, q, n_bad=0, what=""):
     n = len(p)
     assert stats[0] == n, what
     assert stats[3] == n_bad, what
-    Rr, tr, s, d, S = ref_align(p, q)
+    Rr, tr, s, d, m = ref_align(p, q)
+    S = m[17] + m[18]
     kappa = s[0] / (s[1] + d * s[2])
     tol_R = 1024 * EPS * kappa
     tol_t = (2 * tol_R + 64 * EPS) * max(np.abs(p).max(), np.abs(q).max())
@@ -88,16 +66,6 @@ def known_pose(nq, seed, offset=0.0):
     tgt[perm] = q
     dist = np.sqrt(((tgt[perm] - p) ** 2).sum(1))
     return p, tgt, perm, dist
-
-
-def strided(idx, dist, stride):
-    """rows of `stride` slots whose slot 0 is idx / dist and whose other slots
-    would break the fit if they were read"""
-    I = np.full((len(idx), stride), -5, np.int32)
-    D = np.full((len(idx), stride), np.nan)
-    I[:, 0] = idx
-    D[:, 0] = dist
-    return I, D
 
 
 @pytest.mark.parametrize("stride", [1, 8])
@@ -221,26 +189,6 @@ def test_transform_pose_bitexact(gpu, n):
     gpu.sync()
     assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
     assert np.abs(a.cpu().numpy()).max() > 0
-
-
-_L9 = {}
-
-
-def l9_clouds():
-    if not _L9:
-        from navslam.synth import l9_pair
-        src, tgt = l9_pair(16, 256, seed=3)
-        _L9["pair"] = (src.reshape(-1, 3), tgt.reshape(-1, 3))
-    return _L9["pair"]
-
-
-def apply_pose(pose, pts):
-    """k_transform's operation order: t + ((R0 x + R1 y) + R2 z)"""
-    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
-    out = np.empty_like(pts)
-    for i in range(3):
-        out[:, i] = pose[9 + i] + ((pose[3 * i] * x + pose[3 * i + 1] * y) + pose[3 * i + 2] * z)
-    return out
 
 
 def test_icp_steps_match_restatement(gpu, orc):

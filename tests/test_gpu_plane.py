@@ -1,5 +1,5 @@
 """Surface normals, the point-to-plane step and its ICP loop on the GPU
-(plane.hip) against the numpy restatements of tests/plane_ref.py. The
+(plane.hip) against the numpy restatements of tests/reg_ref.py. The
 reference project has none of this, so the restatements are the checkers.
 
 Normals: with l0 <= l1 <= l2 the eigenvalues of the centred covariance, the
@@ -14,13 +14,14 @@ data's magnitudes).
 import numpy as np
 import pytest
 
-from plane_ref import EPS, check_step, knn_numpy, ref_normals, ref_plane
+from reg_ref import (EPS, apply_pose, check_step, knn_numpy, l9_clouds, ref_normals, ref_plane,
+                     rot, strided)
 
 pytestmark = pytest.mark.gpu
 
 # k_normals: at most 1024 blocks of 256 threads, one point per thread and trip
 NORM_ONE_TRIP = 1024 * 256
-# k_plane_moments: at most 1024 blocks of 256 threads, 2 queries per thread and trip
+# the plane step's moments kernel: at most 1024 blocks of 256 threads, 2 queries per thread and trip
 PLANE_ONE_TRIP = 1024 * 256 * 2
 
 
@@ -30,25 +31,6 @@ def gpu():
     g = NavGpu(0)
     yield g
     g.close()
-
-
-def rot(axis, deg):
-    a = np.asarray(axis, np.float64)
-    a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(deg)
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
-
-
-_L9 = {}
-
-
-def l9_clouds():
-    if not _L9:
-        from navslam.synth import l9_pair
-        src, tgt = l9_pair(16, 256, seed=3)
-        _L9["pair"] = (src.reshape(-1, 3), tgt.reshape(-1, 3))
-    return _L9["pair"]
 
 
 # ------------------------------------------------------------------ normals
@@ -259,16 +241,6 @@ def box_pose(nq, seed):
     return p, tgt, nrm, curv, perm, dist
 
 
-def strided(idx, dist, stride):
-    """rows of `stride` slots whose slot 0 is idx / dist and whose other slots
-    would break the fit if they were read"""
-    I = np.full((len(idx), stride), -5, np.int32)
-    D = np.full((len(idx), stride), np.nan)
-    I[:, 0] = idx
-    D[:, 0] = dist
-    return I, D
-
-
 @pytest.mark.parametrize("stride", [1, 8])
 @pytest.mark.parametrize("nq", [5, 6, 64, 65, 4097, PLANE_ONE_TRIP + 1])
 def test_plane_known_pose(gpu, nq, stride):
@@ -412,15 +384,6 @@ def test_plane_deterministic():
 
 
 # ---------------------------------------------------------------------- ICP
-def apply_pose(pose, pts):
-    """k_transform's operation order: t + ((R0 x + R1 y) + R2 z)"""
-    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
-    out = np.empty_like(pts)
-    for i in range(3):
-        out[:, i] = pose[9 + i] + ((pose[3 * i] * x + pose[3 * i + 1] * y) + pose[3 * i + 2] * z)
-    return out
-
-
 def test_icp_plane_steps_match_restatement(gpu, orc):
     src, tgt = l9_clouds()
     gate, iters, vp = 150.0, 4, (0.0, 0.0, 0.0)

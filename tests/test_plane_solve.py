@@ -3,7 +3,7 @@ plane_solve.h) on the host: tests/plane_solve_driver.cpp is compiled against
 the header with the address and undefined-behaviour sanitizers and run as a
 stand-alone program (hex floats in on stdin, results back). The checkers are
 numpy.linalg.eigh for sym3_eig and the numpy restatement ref_plane
-(tests/plane_ref.py) for plane_solve; the reference project has neither."""
+(tests/reg_ref.py) for plane_solve; the reference project has neither."""
 import os
 import subprocess
 
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from plane_ref import EPS, check_step, knn_numpy, plane_moments, ref_normals, ref_plane
+from reg_ref import EPS, check_step, knn_numpy, plane_moments, ref_normals, ref_plane, rot
 
 CSRC = os.path.join(ROOT, "nav-slam_amd", "csrc")
 DRIVER = os.path.join(ROOT, "tests", "plane_solve_driver.cpp")
@@ -30,14 +30,6 @@ def driver(tmp_path_factory):
         assert r.returncode == 0, r.stderr
         return np.array([float.fromhex(w) for w in r.stdout.split()])
     return run
-
-
-def rot(axis, deg):
-    a = np.asarray(axis, np.float64)
-    a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(deg)
-    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
 
 
 # ------------------------------------------------------------------ sym3_eig
