@@ -37,6 +37,8 @@
  *   navgpu_normals_*, navgpu_cloud_normals_*, navgpu_align_plane_*,
  *   navgpu_icp_plane_*     none: surface normals from the k-NN's rows and
  *                          the point-to-plane fit on them
+ *   navgpu_voxel_downsample_*  none: one point per occupied cell of a regular
+ *                          grid (centroid, count, centred covariance sums)
  */
 #ifndef NAVGPU_H
 #define NAVGPU_H
@@ -400,6 +402,48 @@ int navgpu_icp_plane_normals_host(navgpu_ctx *ctx, const double *src,
                                   double max_dist, double max_curv,
                                   const int32_t *mask, double pose[12],
                                   double *hist, double *stats);
+
+/* ---- Voxel-grid downsampling of a cloud ------------------------------------
+ * Not part of the reference interface. DESIGN.md §12.
+ *
+ * One output voxel per occupied cell of a regular grid of edge `voxel` (finite
+ * and > 0, else NAVGPU_EINVAL). With o the origin, a point's cell on each axis
+ * is t = floor((x - o) / voxel) in f64 IEEE arithmetic without contraction. A
+ * point is dropped when a coordinate is not finite, or when a t fails
+ * 0 <= t < 2097152 (21 bits per axis; compared in double before any
+ * conversion). origin: 3 HOST doubles, finite (else NAVGPU_EINVAL), or NULL for
+ * the per-axis minimum over the points whose three coordinates are all finite,
+ * computed on the device. n < 2^31, else NAVGPU_ERANGE.
+ *
+ * The voxels are the distinct keys ix 2^42 + iy 2^21 + iz of the kept points
+ * in ASCENDING KEY ORDER. Voxel j: centroids[3j ..] the mean of its points;
+ * counts[j] (nullable) their number m; cov[6j ..] (nullable) the centred sums
+ * sum (x - c)(x - c)^T about that centroid as xx, xy, xz, yy, yz, zz, a second
+ * pass and not divided by m; cells[3j ..] (nullable) the cell (ix, iy, iz).
+ * labels[i] (nullable) is the voxel of point i, -1 when it was dropped.
+ * stats (7 doubles): the number of voxels; points kept; points dropped as
+ * non-finite; points dropped as out of range; the origin used (3).
+ * cap is the capacity of centroids, counts, cov and cells in voxels: voxels
+ * numbered cap and above are written nowhere, while stats[0] is the true
+ * number and labels holds the true numbers. n == 0, and a cloud whose every
+ * point is dropped, are clean calls that give 0 voxels (the computed origin is
+ * then 0).
+ * A voxel's points are added in an order fixed by the sorted (key, index)
+ * pairs: no floating-point atomics, and the same input gives the same bits on
+ * every run and every context. No host synchronisation; no allocation once the
+ * workspace has grown; the launches depend on n alone, on whether an origin is
+ * given and on whether cov is wanted. Timed as "voxel". */
+int navgpu_voxel_downsample_dev(navgpu_ctx *ctx, const double *pts, size_t n,
+                                double voxel, const double *origin, size_t cap,
+                                double *centroids, int32_t *counts, double *cov,
+                                int32_t *cells, int32_t *labels, double *stats);
+/* The same on host pointers (stats[7] on the host): fills stats, writes the
+ * first min(voxels, cap) voxels and returns NAVGPU_ERANGE when the number of
+ * voxels exceeds cap. */
+int navgpu_voxel_downsample_host(navgpu_ctx *ctx, const double *pts, size_t n,
+                                 double voxel, const double *origin, size_t cap,
+                                 double *centroids, int32_t *counts, double *cov,
+                                 int32_t *cells, int32_t *labels, double *stats);
 
 /* ---- R5 for one arbitrary point array (kdtree.h buildKDTree) ------------
  * pts: n points (AoS), permuted in place into the reference's buildKDTree

@@ -1,9 +1,10 @@
-// navgpu_common.h — what the four translation units of libnavgpu.so share:
+// navgpu_common.h — what the five translation units of libnavgpu.so share:
 // navgpu.hip (per-row mode, curvature, KD build, host plumbing), knn.hip
 // (global-mode grid index and exact k-NN), align.hip (rigid registration
 // on the k-NN's output) and plane.hip (surface normals and point-to-plane
 // registration on it; the two share their step, ICP loop and host staging in
-// reg_step.h). Internal: never installed.
+// reg_step.h) and voxel.hip (voxel-grid downsampling of a cloud). Internal:
+// never installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -249,6 +250,7 @@ enum Slot {
   kQSort, kCellId2, kSRec, kNpg, kGl, kRowTieLazy,
   kAlignPart, kAlignOut, kIcpCur, kIcpIdx, kIcpDist,  // align.hip
   kPlanePart, kPlaneOut, kNormIdx, kNormDist, kPlaneNrm, kPlaneCurv,  // plane.hip
+  kVoxKeys, kVoxVals, kVoxHist, kVoxNum, kVoxPart, kVoxCent, kVoxOut,  // voxel.hip
   kH0 = 100, kH1, kH2, kH3, kH4, kH5,
 };
 

@@ -92,6 +92,10 @@ def _declare(L):
         "navgpu_icp_plane_normals_host": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _vp, C.c_int,
                                                     C.c_double, C.c_double, _vp, _vp, _vp,
                                                     _vp]),
+        "navgpu_voxel_downsample_dev": (C.c_int, [_vp, _vp, _sz, C.c_double, _vp, _sz, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp]),
+        "navgpu_voxel_downsample_host": (C.c_int, [_vp, _vp, _sz, C.c_double, _vp, _sz, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp]),
         "navgpu_kd_build_dev": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_kd_build_host": (C.c_int, [_vp, _vp, _sz, C.c_int]),
         "navgpu_malloc": (C.c_int, [_vp, _sz, C.POINTER(_vp)]),
@@ -425,6 +429,37 @@ class NavGpu:
                 _ptr(stats)), "icp_plane")
         return pose[:9].reshape(3, 3).copy(), pose[9:].copy(), stats, hist
 
+    def voxel_downsample(self, pts, voxel, origin=None, cov=False, cells=False, labels=False,
+                         cap=None):
+        """Voxel-grid downsampling of a cloud (navgpu.h): one point per occupied
+        cell of edge `voxel`, in ascending key order. origin: 3 doubles, or None
+        for the per-axis minimum of the finite points. Returns (centroids[m,3],
+        counts[m], then cov[m,6], cells[m,3] and labels[n] where asked for,
+        stats[7]), the voxel arrays trimmed to the m voxels. cap (default: the
+        number of points) bounds m: more voxels than cap raise NavGpuError."""
+        pts = self._cloud(pts)
+        n = len(pts)
+        cap = n if cap is None else int(cap)
+        org = self._viewpoint(origin)
+        cen = np.zeros((cap, 3))
+        cnt = np.zeros(cap, np.int32)
+        cv = np.zeros((cap, 6)) if cov else None
+        ce = np.zeros((cap, 3), np.int32) if cells else None
+        lab = np.zeros(n, np.int32) if labels else None
+        stats = np.zeros(7)
+        self._check(self.L.navgpu_voxel_downsample_host(
+            self.h, _ptr(pts), n, float(voxel), _ptr(org), cap, _ptr(cen), _ptr(cnt), _ptr(cv),
+            _ptr(ce), _ptr(lab), _ptr(stats)), "voxel_downsample")
+        m = int(stats[0])
+        out = [cen[:m], cnt[:m]]
+        if cov:
+            out.append(cv[:m])
+        if cells:
+            out.append(ce[:m])
+        if labels:
+            out.append(lab)
+        return (*out, stats)
+
     def kd_build(self, pts, depth0=0):
         """Reference buildKDTree permutation of `pts` (returns a new array)."""
         p = np.array(pts, np.float64, order="C").reshape(-1, 3)
@@ -487,6 +522,15 @@ class NavGpu:
             self.h, _ptr(src), nq, _ptr(tgt), nt, _ptr(tgt_normals), _ptr(tgt_curv), iters,
             float(max_dist), float(max_curv), _ptr(mask), _ptr(pose), _ptr(hist), _ptr(stats)),
             "icp_plane_dev")
+
+    def voxel_downsample_dev(self, pts, n, voxel, origin, cap, centroids, counts, cov, cells,
+                             labels, stats):
+        """origin: 3 host doubles or None; the rest device pointers (counts,
+        cov, cells and labels may be None)."""
+        org = self._viewpoint(origin)
+        self._check(self.L.navgpu_voxel_downsample_dev(
+            self.h, _ptr(pts), n, float(voxel), _ptr(org), cap, _ptr(centroids), _ptr(counts),
+            _ptr(cov), _ptr(cells), _ptr(labels), _ptr(stats)), "voxel_downsample_dev")
 
     def kd_build_dev(self, pts, n, depth0=0):
         self._check(self.L.navgpu_kd_build_dev(self.h, _ptr(pts), n, depth0), "kd_build_dev")

@@ -18,7 +18,20 @@ timing hook. Per workload it reports
 The keys of the former align_bench.py output (profiles/align/) are those of
 the uniform_1M workload; those of plane_bench.py (profiles/plane/) are kept.
 Writes the JSON to --out (default profiles/registration/bench.json) and prints
-it on one line."""
+it on one line.
+
+The voxel section (--voxel-only runs it alone) times the
+"voxel" region of voxel_downsample_dev, every output wanted and the origin
+computed, on uniform_pair() at 1,048,576 points with voxel = 20 (about 8
+points per voxel), on the same cloud as one voxel (the long-segment case), and
+on the 128 x 2048 room scan at 100 mm, each beside the stream-copy ceiling of
+the run through a bytes model (per point: 24 B minimum pass, 36 B keys, 8
+passes x 32 B sort, 28 B heads and numbering, 76 B centroid passes, 128 B
+covariance passes = 548 B). Then a 10-iteration icp_plane_dev on the room scan
+at full resolution and with both clouds downsampled at 100 mm (normals on the
+downsampled target): wall time, regions, and the final pose error against the
+true motion of l9_pair's default step. Writes --voxel-out (default
+profiles/voxel/bench_voxel.json)."""
 import argparse
 import json
 import os
@@ -154,8 +167,115 @@ def workload(g, torch, dev, s, t, a, copy_gbs):
     return res
 
 
+VOXEL_BYTES_PER_POINT = 24 + 36 + 8 * 32 + 28 + 76 + 128
+
+
+def pose_error(pose):
+    """translation (mm) and rotation (degrees) error of a 12-double pose
+    against the true motion of l9_pair's default step"""
+    th = np.deg2rad(0.8)
+    Rz = np.array([[np.cos(th), -np.sin(th), 0.0], [np.sin(th), np.cos(th), 0.0],
+                   [0.0, 0.0, 1.0]])
+    Rt = Rz.T
+    tt = -Rt @ np.array([120.0, -40.0, 5.0])
+    Rm = pose[:9].reshape(3, 3)
+    c = (np.trace(Rm @ Rt.T) - 1.0) / 2.0
+    return (float(np.linalg.norm(pose[9:] - tt)),
+            float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0)))))
+
+
+def voxel_timed(g, torch, dev, pts, voxel, a, copy_gbs):
+    """the "voxel" region on one cloud, every output wanted, origin computed"""
+    n = len(pts)
+    d = torch.from_numpy(np.ascontiguousarray(pts)).to(dev)
+    cen = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    cov = torch.zeros((n, 6), dtype=torch.float64, device=dev)
+    cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    cells = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    lab = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = torch.zeros(7, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    ts = timed(g, "voxel", a.calls, a.warmup,
+               lambda: g.voxel_downsample_dev(d, n, voxel, None, n, cen, cnt, cov, cells, lab, st))
+    res = region_stats(ts, VOXEL_BYTES_PER_POINT * n, copy_gbs)
+    stats = st.cpu().numpy()
+    m = int(stats[0])
+    res.update(points=n, voxel=voxel, voxels=m, kept=int(stats[1]),
+               largest_count=int(cnt[:m].max().item()) if m else 0)
+    return res, cen[:m].clone()
+
+
+def room_loop(g, torch, dev, src, tgt, a, gate=150.0):
+    """10 iterations of icp_plane_dev, the normals (k = 8, viewpoint 0) made
+    first and outside the timed loop"""
+    nq, nt = len(src), len(tgt)
+    nrm = torch.zeros((nt, 3), dtype=torch.float64, device=dev)
+    curv = torch.zeros(nt, dtype=torch.float64, device=dev)
+    g.cloud_normals_dev(tgt, nt, KN, (0.0, 0.0, 0.0), nrm, curv)
+    g.sync()
+    g.knn_check()
+    iters = 10
+    pose0 = np.concatenate([np.eye(3).ravel(), np.zeros(3)])
+    pose = torch.from_numpy(pose0.copy()).to(dev)
+    stats = torch.zeros((iters, 6), dtype=torch.float64, device=dev)
+    regions = ("icp_transform", "knn_build", "knn_query", "align_plane")
+    per = {r: [] for r in regions}
+    wall = []
+    g.timing_select(None)
+    for r in regions:
+        g.timing_read(r)
+    for i in range(2 + a.icp_runs):
+        pose.copy_(torch.from_numpy(pose0))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        g.icp_plane_dev(src, nq, tgt, nt, nrm, curv, iters, gate, np.inf, None, pose, None, stats)
+        g.sync()
+        w = (time.perf_counter() - t0) * 1e3
+        got = {r: g.timing_read(r)[0] for r in regions}
+        if i >= 2:
+            wall.append(w)
+            for r in regions:
+                per[r].append(got[r])
+    g.knn_check()
+    et, er = pose_error(pose.cpu().numpy())
+    st = stats.cpu().numpy()
+    return {"source_points": nq, "target_points": nt, "iters": iters, "runs": a.icp_runs,
+            "max_dist": gate, "wall_ms_med": med(wall),
+            "regions_ms_med": {r: med(per[r]) for r in regions},
+            "knn_query_share_of_wall": round(float(np.median(per["knn_query"]) /
+                                                   np.median(wall)), 4),
+            "pairs_last": int(st[-1, 0]), "rms_last": float(st[-1, 1]),
+            "pose_error_mm": round(et, 4), "pose_error_deg": round(er, 5)}
+
+
+def voxel_section(g, torch, dev, a, copy_gbs):
+    res = {"bytes_model_per_point": VOXEL_BYTES_PER_POINT}
+    s, _ = uniform_pair(512, 2048)
+    s = s.reshape(-1, 3)
+    res["uniform_1M_voxel20"], _ = voxel_timed(g, torch, dev, s, 20.0, a, copy_gbs)
+    res["uniform_1M_one_voxel"], _ = voxel_timed(g, torch, dev, s, 1.0e6, a, copy_gbs)
+    res["one_voxel_over_uniform"] = round(res["uniform_1M_one_voxel"]["ms_med"] /
+                                          res["uniform_1M_voxel20"]["ms_med"], 4)
+    s, t = l9_pair(128, 2048)
+    s, t = s.reshape(-1, 3), t.reshape(-1, 3)
+    res["l9_128x2048_voxel100"], t_ds = voxel_timed(g, torch, dev, t, 100.0, a, copy_gbs)
+    res["l9_128x2048_voxel100_source"], s_ds = voxel_timed(g, torch, dev, s, 100.0, a, copy_gbs)
+    src = torch.from_numpy(np.ascontiguousarray(s)).to(dev)
+    tgt = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    torch.cuda.synchronize()
+    res["icp_plane10_full"] = room_loop(g, torch, dev, src, tgt, a)
+    res["icp_plane10_voxel100"] = room_loop(g, torch, dev, s_ds.contiguous(), t_ds.contiguous(), a)
+    res["voxel100_over_full_wall"] = round(res["icp_plane10_voxel100"]["wall_ms_med"] /
+                                           res["icp_plane10_full"]["wall_ms_med"], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--voxel-out",
+                    default=os.path.join(ROOT, "profiles", "voxel", "bench_voxel.json"))
+    ap.add_argument("--voxel-only", action="store_true",
+                    help="run the voxel section alone")
     ap.add_argument("--out",
                     default=os.path.join(ROOT, "profiles", "registration", "bench.json"))
     ap.add_argument("--calls", type=int, default=60)
@@ -183,12 +303,25 @@ def main():
     res["stream_copy"] = {"bytes_each_way": nb, "ms_med": med(ts), "GBps": round(copy_gbs, 1)}
     del ca, cb
 
+    vox = {"calls": a.calls, "warmup": a.warmup, "stream_copy": res["stream_copy"],
+           **voxel_section(g, torch, dev, a, copy_gbs)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.voxel_out)), exist_ok=True)
+    with open(a.voxel_out, "w") as f:
+        json.dump(vox, f, indent=1)
+        f.write("\n")
+    if a.voxel_only:
+        g.timing(False)
+        g.close()
+        print(json.dumps(vox), flush=True)
+        return
+
     s, t = uniform_pair(512, 2048)
     res["uniform_1M"] = workload(g, torch, dev, s.reshape(-1, 3), t.reshape(-1, 3), a, copy_gbs)
     s, t = l9_pair(128, 2048)
     res["l9_128x2048"] = workload(g, torch, dev, s.reshape(-1, 3), t.reshape(-1, 3), a, copy_gbs)
     g.timing(False)
     g.close()
+    res["voxel"] = vox
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
